@@ -1,10 +1,14 @@
 """Benchmark: SPGG hot path on MI355X, agent-steps/s (+ roofline, CPU baseline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--rng philox]
+                    [--dump-outputs DIR] [--full]
 
-Default window: the driver's, iterations 6-25 (--warmup 5 --steps 20); the line also carries
-the steady window 401-600 (eps at eps_min), the whole 10,000-iteration run (full_run) and the
-MT19937 product path (mt19937).
+Default window: the driver's, iterations 6-25 (--warmup 5 --steps 20).  A plain run sets up,
+warms up, times the K steps and prints the line (headline figure + its roofline).  --full adds
+the legs that take runs of their own: the steady window 401-600 (eps at eps_min), the whole
+10,000-iteration run (full_run), the MT19937 product path (mt19937) and the CPU baseline.
+--dump-outputs DIR writes what the timed window left behind (every replica's S, R, Q after its
+last step and the window's cooperation trace) as DIR/<name>.npy.
 
 A "step" is one iteration of the reference's run loop (src/model/spgg.py:368-592)
 over every replica of the batch resident in HBM.  Default workload is cfg3 of
@@ -232,29 +236,70 @@ def full_run(L, M2, state, reps, rng, streams, T, offset, turn=256):
             "note": "whole run through BatchEngine.run (absorbing stops, group retirement, host syncs, flush)"}
 
 
+DUMP_ARRAY_BYTES = 20 * 10 ** 6    # per dumped array; S, R, Q + the small ones stay under 64 MB
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, eng, stop, trace, coop):
+    """What the timed window left behind, as float32 / float64 .npy files in out_dir: the state a
+    caller of BatchEngine.step receives once the run is closed (the flush of the last executed
+    iteration's deferred NI term, as BatchEngine.run ends) -- every replica's strategies S
+    (R, L, L), reputations R (R, L, L) and Q tables Q (R, L, L, 2, 2) -- plus the window's
+    cooperation-rate trace, the final rates and the absorbing-stop iterations.  An array over
+    DUMP_ARRAY_BYTES is written as a fixed sample of its flattened elements (sorted indices drawn
+    without replacement by RandomState(DUMP_SAMPLE_SEED), the same for every run of one shape)."""
+    import numpy as np
+    import torch
+    eng.flush()
+    torch.cuda.synchronize()
+    eng.stopped = np.asarray(stop).astype(np.int64)
+    eng.check_status()
+    fin = [eng.final_state(k) for k in range(eng.R)]
+    arrays = {"S": np.stack([f[2] for f in fin]).astype(np.float32),
+              "R": np.stack([f[1] for f in fin]).astype(np.float64),
+              "Q": np.stack([f[0] for f in fin]).astype(np.float64),
+              "coop_trace": np.nan_to_num(trace, nan=-1.0).astype(np.float64),   # -1: after an absorbing stop
+              "coop_final": np.asarray(coop, dtype=np.float64),
+              "stop_iter": np.asarray(stop).astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            idx = np.random.RandomState(DUMP_SAMPLE_SEED).choice(a.size, DUMP_ARRAY_BYTES // a.itemsize,
+                                                                 replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # the driver's own window (bench.py --steps 20 --warmup 5: iterations 6-25, eps 0.48 -> 0.40,
-    # right after the engine is made); the line also carries the steady window 401-600 (eps at
-    # eps_min from t = 390: what a 10,000-iteration run spends >96 % of its iterations in) and the
-    # whole run
+    # right after the engine is made); with --full the line also carries the steady window 401-600
+    # (eps at eps_min from t = 390: what a 10,000-iteration run spends >96 % of its iterations in)
+    # and the whole run
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-steady", action="store_true", help="skip the steady window (iterations 401-600)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the steady window, the MT19937 "
+                         "window, the config's whole run and the CPU baseline (each with its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed window left behind (S, R, Q of every replica after its last "
+                         "step, the cooperation trace) as DIR/<name>.npy (rank k of several: DIR/rank<k>/)")
+    ap.add_argument("--no-steady", action="store_true",
+                    help="with --full: skip the steady window (iterations 401-600)")
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--rng", default="philox", choices=["philox", "mt19937"])
     ap.add_argument("--streams", type=int, default=None,
                     help="replica groups on concurrent HIP streams (default: auto)")
     ap.add_argument("--replicas", type=int, default=None,
                     help="experiment: first N replicas of the workload grid (cycled)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--full-run", type=int, default=-1,
-                    help="also time the config's whole run (iterations; -1: BASELINE.json's, when it "
+                    help="with --full: time the config's whole run (iterations; -1: BASELINE.json's, when it "
                          "takes under a minute at the measured step time; 0: off)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--no-mt", action="store_true",
-                    help="skip the MT19937 (product-path) window reported beside a Philox line")
+                    help="with --full: skip the MT19937 (product-path) window reported beside a Philox line")
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -291,7 +336,7 @@ def main(argv=None):
         desc += f" [experiment: {args.replicas} replicas]"
     K, W = args.steps, args.warmup
 
-    def window(rng, W=W, K=K):
+    def window(rng, W=W, K=K, dump=None):
         """W untimed + K timed iterations of a fresh engine in `rng` mode (barrier +
         synchronize on both sides; max over ranks): the executed agent-steps, times, layout."""
         eng = E.BatchEngine(L, K + W, reps, use_second_order=M2, state_representation=state, rng=rng,
@@ -345,11 +390,16 @@ def main(argv=None):
         out = dict(agent_steps=agent_steps, agent_steps_all=agent_steps_all, wall=wall, wall_max=wall_max,
                    dev_ms=dev_ms, coop=coop, trace=trace, mt_layout=mt_layout, resident=eng.resident,
                    groups=eng.G, waves=eng.waves, persistent=eng.persistent)
+        if dump:
+            dump_outputs(dump, eng, stop, trace, coop)
         eng.close()   # before the next engine, the full run and the CPU baseline's worker processes
         return out
 
     n_agents = len(reps) * L * L
-    main_w = window(args.rng)
+    dump_dir = args.dump_outputs
+    if dump_dir and world > 1:
+        dump_dir = os.path.join(dump_dir, f"rank{rank}")
+    main_w = window(args.rng, dump=dump_dir)
     agent_steps, wall, dev_ms = main_w["agent_steps"], main_w["wall"], main_w["dev_ms"]
     agent_steps_all, wall_max, mt_layout = main_w["agent_steps_all"], main_w["wall_max"], main_w["mt_layout"]
     # the path's only collective: every rank's per-replica final
@@ -375,9 +425,9 @@ def main(argv=None):
                    f"(Q rows held in registers, a per-replica barrier between iterations)" if persistent else
                    f"spgg_step_kernel, {resident} concurrent launches per iteration (one per replica group/stream)")
     # the drop-in SPGG.run / sweep path: the device MT19937 stream, bit-identical to the reference
-    mt_w = window("mt19937") if args.rng == "philox" and not args.no_mt else None
+    mt_w = window("mt19937") if args.full and args.rng == "philox" and not args.no_mt else None
     steady = None
-    if not args.no_steady and (W, K) != (400, 200):
+    if args.full and not args.no_steady and (W, K) != (400, 200):
         steady = window(args.rng, 400, 200)
 
     traffic = None
@@ -420,7 +470,7 @@ def main(argv=None):
                          "device_ms_per_step": per_step_dev_s * 1e3},
         }
         T_full = FULL_RUN_ITERS.get(args.config, 0) if args.full_run < 0 else args.full_run
-        if args.full_run < 0 and wall_max / K * T_full > 60.0:
+        if not args.full or (args.full_run < 0 and wall_max / K * T_full > 60.0):
             T_full = 0
         if steady:
             sd = steady["dev_ms"] / 1e3 / 200
@@ -442,7 +492,7 @@ def main(argv=None):
             line["full_run"] = full_run(L, M2, state, reps, args.rng, args.streams, T_full, 0)
             if mt_w:
                 line["mt19937"]["full_run"] = full_run(L, M2, state, reps, "mt19937", args.streams, T_full, 0)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(L, M2, state, reps, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if dist:

@@ -5,7 +5,7 @@
 cd "$GRAFT_REPO_ROOT"; O="$GRAFT_REPO_ROOT/gpurun_out/cfgs"; mkdir -p "$O"; export TMPDIR=/tmp
 : > $O/lines.txt
 for c in ${@:-cfg2 run100 cfg4 cfg5}; do
-  timeout -k 10 300 python bench.py --config $c --no-cpu-baseline > "$O/bench_$c.json" 2> "$O/bench_$c.err" \
+  timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline > "$O/bench_$c.json" 2> "$O/bench_$c.err" \
     || { tail -5 "$O/bench_$c.err"; exit 1; }
   python -c "
 import json; d=json.loads(open('$O/bench_$c.json').read().strip().splitlines()[-1]); m=d['mt19937']; s=d['steady_window']

@@ -17,7 +17,7 @@ for r in $(seq 1 $R); do
       env:*) env_kv="${L#env:}"; tag="$env_kv" ;;   # the in-tree library with a tuning knob set
       *) env_lib="$GRAFT_REPO_ROOT/$L" ;;
     esac
-    env SPGG_LIB="$env_lib" ${env_kv:+SPGG_TUNING=1 "$env_kv"} timeout -k 10 180 python bench.py --no-cpu-baseline --no-mt --full-run 0 "$@" > "$O/tmp.json" 2> "$O/tmp.err" \
+    env SPGG_LIB="$env_lib" ${env_kv:+SPGG_TUNING=1 "$env_kv"} timeout -k 10 180 python bench.py --full --no-cpu-baseline --no-mt --full-run 0 "$@" > "$O/tmp.json" 2> "$O/tmp.err" \
       || { echo "$tag failed"; tail -5 "$O/tmp.err"; exit 1; }
     python - "$O/tmp.json" "$tag" "$r" >> "$O/lines.txt" <<'PY'
 import json, sys

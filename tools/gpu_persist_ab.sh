@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r6/ab; mkdir -p $O; export TMPDIR=/tmp
 : > $O/lines.txt
 for c in ${CFGS:-cfg5 cfg4 cfg2}; do
   for p in 1 0; do
-    SPGG_PERSIST=$p timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --no-mt --full-run 3000 \
+    SPGG_PERSIST=$p timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --no-mt --full-run 3000 \
       > $O/bench_${c}_p$p.json 2> $O/bench_${c}_p$p.err || { tail -5 $O/bench_${c}_p$p.err; exit 1; }
     python -c "
 import json; d=json.loads(open('$O/bench_${c}_p$p.json').read().strip().splitlines()[-1]); s=d['steady_window']; f=d['full_run']

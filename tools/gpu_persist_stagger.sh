@@ -6,7 +6,7 @@ export SPGG_TUNING=1
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r6/stagger; mkdir -p $O; export TMPDIR=/tmp
 C=${CFG:-cfg5}; : > $O/lines.txt
 run() {  # name persist lib
-  SPGG_LIB=$3 SPGG_PERSIST=$2 timeout -k 10 120 python bench.py --config $C --no-cpu-baseline --no-mt --full-run 0 \
+  SPGG_LIB=$3 SPGG_PERSIST=$2 timeout -k 10 120 python bench.py --full --config $C --no-cpu-baseline --no-mt --full-run 0 \
     > $O/$1.json 2> $O/$1.err || { tail -3 $O/$1.err; exit 1; }
   python -c "
 import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); s=d['steady_window']

@@ -9,7 +9,7 @@
 #   trace_mt/           kernel statistics of the MT19937 window (step, generator, jump kernels)
 #   traffic: tools/gpu_traffic_windows.sh (separate FETCH_SIZE / WRITE_SIZE passes per window)
 cd "$GRAFT_REPO_ROOT"; O="$GRAFT_REPO_ROOT/gpurun_out/round"; mkdir -p "$O"; export TMPDIR=/tmp
-timeout -k 10 500 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { echo "bench failed"; tail "$O/bench.err"; exit 1; }
+timeout -k 10 500 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { echo "bench failed"; tail "$O/bench.err"; exit 1; }
 cat "$O/bench.json"
 timeout -k 10 300 python bench.py --no-cpu-baseline --no-mt --no-steady --full-run 0 --streams 1 > "$O/bench_s1.json" 2> "$O/bench_s1.err" || { echo "bench s1 failed"; tail "$O/bench_s1.err"; exit 1; }
 cat "$O/bench_s1.json"
