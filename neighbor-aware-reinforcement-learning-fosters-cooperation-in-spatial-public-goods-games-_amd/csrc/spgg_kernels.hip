@@ -44,6 +44,7 @@
 #include "spgg_test.h"
 #include "spgg_device.h"
 #include "spgg_mt.h"
+#include "spgg_clusters.h"
 
 using namespace spgg;
 
@@ -3581,6 +3582,25 @@ int spgg_payoff(spgg_ctx* c, int32_t t, double* out, void* stream) {
   hipLaunchKernelGGL(spgg_payoff_kernel, grid, dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
                      c->buf.S[(t - 1) & 1], c->d_params, out, c->cfg.L, c->n);
   return hip_check(c, hipGetLastError(), "spgg_payoff launch");
+}
+
+int spgg_clusters_max_side(const spgg_ctx* c, int32_t* side) {
+  if (!c || !side) return SPGG_E_ARG;
+  *side = spgg_cl::kMaxSide;
+  return SPGG_OK;
+}
+
+int spgg_clusters(spgg_ctx* c, int32_t t, int32_t periodic, int32_t* sizes, int32_t* rec, int64_t rec_stride,
+                  void* stream) {
+  if (!c || !rec) return fail(c, SPGG_E_ARG, "null argument");
+  if (!c->bound) return fail(c, SPGG_E_STATE, "spgg_clusters before bind");
+  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_clusters: bad t");
+  if (c->cfg.L > spgg_cl::kMaxSide)
+    return fail(c, SPGG_E_ARG, "spgg_clusters: L = " + std::to_string(c->cfg.L) + " exceeds the supported side " +
+                                   std::to_string(spgg_cl::kMaxSide) + " (the lattice is labelled in LDS)");
+  spgg_cl::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, periodic, sizes, rec,
+                        rec_stride, reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_clusters launch");
 }
 
 int spgg_status(const spgg_ctx* c, uint32_t* flags) {

@@ -214,6 +214,34 @@ def plan_groups(R: int, L: int, bytes_per_replica: int, cache_bytes: int, stream
     return waves, groups, resident
 
 
+def host_cluster_sizes(S, periodic: bool = False) -> np.ndarray:
+    """int64 sizes of the 4-connected cooperator (S == 0) clusters of one lattice in label order
+    (ascending smallest raster index), on the host: scipy.ndimage.label (spgg.py:631-633);
+    periodic merges its labels across the two seams.  The path of lattices above the device
+    labelling's supported side (spgg_clusters_max_side)."""
+    from scipy.ndimage import label
+    lab, k = label(np.asarray(S) == 0)
+    counts = np.bincount(lab.ravel(), minlength=k + 1).astype(np.int64)
+    if not periodic or k == 0:
+        return counts[1:]
+    root = np.arange(k + 1)
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+
+    for a, b in list(zip(lab[0], lab[-1])) + list(zip(lab[:, 0], lab[:, -1])):
+        if a and b:
+            ra, rb = find(a), find(b)
+            if ra != rb:
+                root[max(ra, rb)] = min(ra, rb)   # the label met first in raster order stays
+    owner = np.array([find(a) for a in range(k + 1)])
+    merged = np.bincount(owner, weights=counts, minlength=k + 1).astype(np.int64)
+    return merged[(owner == np.arange(k + 1)) & (np.arange(k + 1) > 0)]
+
+
 # Library-made streams (spgg_stream_create) are pooled per library and device and outlive their
 # engine: torch's pinned-memory allocator keeps the events of a pinned buffer's copies (run()'s
 # stop flags) and queries them when it allocates again, so a stream destroyed under such an event
@@ -324,6 +352,8 @@ class BatchEngine:
         self.snapshots = [dict() for _ in range(self.R)]
         self.png_frames = [dict() for _ in range(self.R)]
         self._flushed = False
+        self._cl_cache = {}        # periodic -> per-replica final cluster sizes (until the next step)
+        self.cl_every, self.cl_periodic, self.cl_rec = 0, False, None   # in-run record (run)
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -470,6 +500,9 @@ class BatchEngine:
         on, cap = ctypes.c_int32(), ctypes.c_int32()
         C.check(self.lib.spgg_persistent(self.ctx, ctypes.byref(on), ctypes.byref(cap)), self.ctx, "spgg_persistent")
         self.persistent, self.persist_capacity = bool(on.value), int(cap.value)
+        side = ctypes.c_int32()
+        C.check(self.lib.spgg_clusters_max_side(self.ctx, ctypes.byref(side)), self.ctx, "spgg_clusters_max_side")
+        self.clusters_max_side = int(side.value)   # device labelling up to this lattice side
 
     def _draw_layout(self, ctx):
         """(ring slots, u32 words per replica and slot, key-snapshot slots) of the draw records."""
@@ -599,6 +632,7 @@ class BatchEngine:
         n_steps = min(n_steps, self.T - self.t + 1)
         if n_steps <= 0:
             return 0
+        self._cl_cache = {}
         if self.rng == "inject":
             for _ in range(n_steps):
                 self._inject(self.t)
@@ -683,7 +717,8 @@ class BatchEngine:
         return self._loop
 
     def run(self, chunk: int = 256, snapshots: bool = True, png: bool = False,
-            progress: Optional[Callable[[int], None]] = None):
+            progress: Optional[Callable[[int], None]] = None, clusters_every: int = 0,
+            clusters_periodic: bool = False):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -692,7 +727,24 @@ class BatchEngine:
         turn is already enqueued (up to `chunk` step launches that return after their loads,
         plus MT19937 generator chunks), and a group is retired one turn late.  Absorbed
         replicas' launches change nothing, so results are unaffected; only the wall time of a
-        run that absorbs early carries that turn.  Snapshot iterations sync."""
+        run that absorbs early carries that turn.  Snapshot iterations sync.
+
+        clusters_every = k > 0: the cluster record of S_t (spgg_clusters: number of cooperator
+        clusters, largest cluster, C-D bonds; clusters_periodic: wrapped lattice) is taken at
+        t = 1, 1+k, 1+2k, ... on each replica group's own stream between the step launches of
+        t-1 and t (a turn boundary there, no host sync; the stop-flag copies stay `chunk`
+        iterations apart); read it with cluster_histories().  With 0 nothing else is enqueued
+        than before."""
+        every = int(clusters_every)
+        if every < 0:
+            raise ValueError("clusters_every must be >= 0")
+        if every and self.L > self.clusters_max_side:
+            raise ValueError(f"clusters_every: the device labels lattices up to side {self.clusters_max_side}, "
+                             f"L = {self.L} (label snapshots on the host: engine.host_cluster_sizes)")
+        if every and (self.cl_rec is None or (every, bool(clusters_periodic)) != (self.cl_every, self.cl_periodic)):
+            # a run continued with the same settings keeps its record and its iterations
+            self.cl_rec = torch.zeros((self.R, self.T + 2, 3), dtype=torch.int32, device=self.dev)
+            self.cl_every, self.cl_periodic, self._cl_t0 = every, bool(clusters_periodic), self.t
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -705,8 +757,12 @@ class BatchEngine:
         pending = []   # (event, slot) of the stop-flag copies in flight (<= 2: this turn's, the last one's)
         turn = 0
         done = False
+        t_rec0 = self._cl_t0 if every else 0   # the record's iterations: t_rec0, t_rec0 + every, ...
+        check_at = self.t + chunk  # the stop flags are copied every `chunk` iterations and at stops
         with torch.cuda.stream(loop):
             while self.t <= self.T and not done:
+                if every and (self.t - t_rec0) % every == 0:
+                    self._record_clusters(self.t)
                 if self.t in stops:
                     self._capture(self.t, snapshots and self.t in SNAPSHOT_ITERS,
                                   png and (self.t - 1) in PNG_ITERS)
@@ -714,10 +770,15 @@ class BatchEngine:
                     done = self._note_stops(self.stop_iter.cpu().numpy())
                     if done:
                         break
-                nxt = min([s for s in stops if s > self.t] + [self.t + chunk, self.T + 1])
+                nxt = min([s for s in stops if s > self.t] + [check_at, self.T + 1])
+                if every:
+                    nxt = min(nxt, self.t + every - (self.t - t_rec0) % every)
                 self.step(nxt - self.t)
                 if progress:
                     progress(self.t - 1)
+                if self.t < check_at and self.t <= self.T and self.t not in stops:
+                    continue       # a turn boundary of the cluster record only
+                check_at = self.t + chunk
                 slot, turn = turn & 1, turn + 1
                 flags[slot].copy_(self.stop_iter, non_blocking=True)
                 ev = torch.cuda.Event()
@@ -792,6 +853,64 @@ class BatchEngine:
         self._enqueue(lambda g, s: C.check(
             self.lib.spgg_payoff(g["ctx"], int(t), self.P_buf[g["r0"]].data_ptr(), s), g["ctx"], "spgg_payoff"))
         return self.P_buf.cpu().numpy().reshape(self.R, self.L, self.L)
+
+    # -- clusters ------------------------------------------------------------
+    def _clusters(self, t, periodic, sizes, rec, row, stride):
+        """Enqueue spgg_clusters of S_t on every group's stream: sizes (R, n) int32 or None,
+        the records into rec[k].view(-1)[row:row + 3] (stride int32 between replicas)."""
+        def one(g, s):
+            r0 = g["r0"]
+            C.check(self.lib.spgg_clusters(
+                g["ctx"], int(t), int(bool(periodic)), sizes[r0].data_ptr() if sizes is not None else None,
+                rec.data_ptr() + 4 * (r0 * stride + row), stride, s), g["ctx"], "spgg_clusters")
+        self._enqueue(one)
+
+    def _record_clusters(self, t):
+        """The in-run record of S_t into row t of cl_rec (run(clusters_every=...))."""
+        self._clusters(t, self.cl_periodic, None, self.cl_rec, 3 * t, (self.T + 2) * 3)
+
+    def cluster_sizes(self, k, periodic: bool = False) -> np.ndarray:
+        """int64 sizes of replica k's cooperator clusters in the state final_state(k) returns, in
+        label order (ascending smallest raster index: scipy.ndimage.label's, spgg.py:631-633);
+        shape (0,) without a cooperator.  periodic=False: the lattice edge is a wall (the
+        reference's dataset); True: it wraps, as the dynamics do.  Labelled on the device, all
+        replicas at once (one spgg_clusters launch per replica group) and cached until the engine
+        steps again; lattices above the supported side are labelled on the host, same result."""
+        periodic = bool(periodic)
+        if self.L > self.clusters_max_side:
+            return host_cluster_sizes(self.final_state(k)[2], periodic)
+        if periodic not in self._cl_cache:
+            if getattr(self, "_cl_sizes", None) is None:
+                self._cl_sizes = torch.empty((self.R, self.n), dtype=torch.int32, device=self.dev)
+                self._cl_final = torch.empty((self.R, 3), dtype=torch.int32, device=self.dev)
+            self._clusters(self.t, periodic, self._cl_sizes, self._cl_final, 0, 3)
+            flat = self._cl_sizes.view(-1)
+            vals = flat[flat > 0].cpu().numpy().astype(np.int64)   # compacted on the device
+            count = self._cl_final[:, 0].cpu().numpy()
+            if np.any(count < 0):
+                raise C.SpggError(f"spgg_clusters: replicas {np.nonzero(count < 0)[0].tolist()} ran into the "
+                                  f"labelling's pass cap ({C.CLUSTERS_MAX_PASSES})")
+            self._cl_cache[periodic] = np.split(vals, np.cumsum(count)[:-1])
+        return self._cl_cache[periodic][k]
+
+    def cluster_histories(self):
+        """Per replica, the in-run cluster record of run(clusters_every=k): cluster_history_iters
+        (the observed iterations t <= last_iteration, so a replica absorbed at s keeps the record
+        of S_s if s was observed), cluster_count_history, largest_cluster_history and
+        cd_bond_history (C-D bonds of the wrapped lattice), all int64."""
+        if not self.cl_every or self.cl_rec is None:
+            raise ValueError("cluster_histories: run(clusters_every=k) with k > 0 first")
+        rec = self.cl_rec.cpu().numpy().astype(np.int64)
+        out = []
+        for k in range(self.R):
+            its = np.arange(self._cl_t0, self.last_iteration(k) + 1, self.cl_every, dtype=np.int64)
+            r = rec[k, its]
+            if np.any(r[:, 0] < 0):
+                raise C.SpggError(f"spgg_clusters: replica {k} ran into the labelling's pass cap "
+                                  f"({C.CLUSTERS_MAX_PASSES}) at iterations {its[r[:, 0] < 0].tolist()}")
+            out.append(dict(cluster_history_iters=its, cluster_count_history=r[:, 0].copy(),
+                            largest_cluster_history=r[:, 1].copy(), cd_bond_history=r[:, 2].copy()))
+        return out
 
     def finalize_history(self):
         """Derived history slots (payoff sums, w_P*P, w_rep*rr, reward over D) of every

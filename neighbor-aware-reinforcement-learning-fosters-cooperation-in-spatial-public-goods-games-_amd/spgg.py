@@ -32,6 +32,12 @@ class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
+    # k > 0: also record the cooperator clusters of S_t (count, largest, C-D bonds) at
+    # t = 1, 1+k, ... on the device and write them as four more datasets (CLUSTER_DATASETS);
+    # 0: the reference's file.  The clusters of the record wrap with the lattice if
+    # cluster_history_periodic (the final cluster_sizes dataset never does: spgg.py:631).
+    cluster_history_every = 0
+    cluster_history_periodic = False
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -138,8 +144,12 @@ class SPGG:
         snapshots_dir = os.path.join(self.folder, 'plots', 'snapshots') if self.folder else 'snapshots'
         os.makedirs(snapshots_dir, exist_ok=True)
         try:
-            eng.run(snapshots=True, png=self.save_png)
+            every = int(self.cluster_history_every or 0)
+            eng.run(snapshots=True, png=self.save_png, clusters_every=every,
+                    clusters_periodic=bool(self.cluster_history_periodic))
             hist = eng.histories()[0]
+            clusters = eng.cluster_sizes(0)   # labelled on the device (host above its supported side)
+            cluster_hist = eng.cluster_histories()[0] if every > 0 else None
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -169,7 +179,8 @@ class SPGG:
 
         # the datasets last: the reference fills its file after the loop, so a write
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
-        write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions)
+        write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
+                       clusters=clusters, cluster_hist=cluster_hist)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -184,10 +195,19 @@ HISTORY_DATASETS = ("it_records_final", "epsilon_history_final", "rep_avg_histor
                     "reputation_reward_ratio", "avg_reward_C_history", "avg_reward_D_history")
 
 
-def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions):
+CLUSTER_DATASETS = ("cluster_history_iters", "cluster_count_history", "largest_cluster_history",
+                    "cd_bond_history")
+
+
+def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
+                   cluster_hist=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
-    the final state.  Shared by SPGG.run and the batched sweep runner."""
+    the final state.  Shared by SPGG.run and the batched sweep runner.
+
+    clusters: the final cluster sizes (BatchEngine.cluster_sizes) instead of labelling S on the
+    host here; cluster_hist: the in-run cluster record (BatchEngine.cluster_histories), written
+    as the CLUSTER_DATASETS after the reference's own.  The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
             Ri, Si = snaps[i]
@@ -217,7 +237,11 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions):
         h, bins = np.histogram(R, bins=20, range=(R_min, R_max))
         data_file.create_dataset("rep_hist_final", data=h)
         data_file.create_dataset("rep_bins_final", data=bins)
-        data_file.create_dataset("cluster_sizes", data=cluster_sizes(S))
+        data_file.create_dataset("cluster_sizes", data=cluster_sizes(S) if clusters is None
+                                 else np.asarray(clusters, dtype=np.int64))
+        if cluster_hist is not None:
+            for name in CLUSTER_DATASETS:
+                data_file.create_dataset(name, data=np.asarray(cluster_hist[name], dtype=np.int64))
 
 
 def track_positions(L):
