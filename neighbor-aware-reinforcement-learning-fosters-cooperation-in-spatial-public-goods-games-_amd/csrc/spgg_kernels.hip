@@ -45,6 +45,7 @@
 #include "spgg_device.h"
 #include "spgg_mt.h"
 #include "spgg_clusters.h"
+#include "spgg_correlations.h"
 
 using namespace spgg;
 
@@ -3601,6 +3602,27 @@ int spgg_clusters(spgg_ctx* c, int32_t t, int32_t periodic, int32_t* sizes, int3
   spgg_cl::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, periodic, sizes, rec,
                         rec_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_clusters launch");
+}
+
+int spgg_correlations_max_side(const spgg_ctx* c, int32_t* side) {
+  if (!c || !side) return SPGG_E_ARG;
+  *side = spgg_co::kMaxSide;
+  return SPGG_OK;
+}
+
+int spgg_correlations(spgg_ctx* c, int32_t t, int32_t max_d, int32_t* out, int64_t out_stride, void* stream) {
+  if (!c || !out) return fail(c, SPGG_E_ARG, "null argument");
+  if (!c->bound) return fail(c, SPGG_E_STATE, "spgg_correlations before bind");
+  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_correlations: bad t");
+  if (c->cfg.L > spgg_co::kMaxSide)
+    return fail(c, SPGG_E_ARG, "spgg_correlations: L = " + std::to_string(c->cfg.L) + " exceeds the supported side " +
+                                   std::to_string(spgg_co::kMaxSide) + " (the lattice is packed into LDS)");
+  if (max_d < 0 || max_d > c->cfg.L / 2)
+    return fail(c, SPGG_E_ARG, "spgg_correlations: max_d = " + std::to_string(max_d) + " outside 0 .. L / 2 = " +
+                                   std::to_string(c->cfg.L / 2));
+  spgg_co::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, max_d, out, out_stride,
+                  reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_correlations launch");
 }
 
 int spgg_status(const spgg_ctx* c, uint32_t* flags) {

@@ -242,6 +242,50 @@ def host_cluster_sizes(S, periodic: bool = False) -> np.ndarray:
     return merged[(owner == np.arange(k + 1)) & (np.arange(k + 1) > 0)]
 
 
+def host_pair_counts(S, max_d=None) -> np.ndarray:
+    """int64 (2, D+1) cooperator pair counts of one lattice on the host, D = max_d (None: L // 2):
+    with c = 1 where bit 0 of S is 0, [0, d] = sum(c & roll(c, -d, axis=1)) (pairs d apart along
+    a row) and [1, d] = sum(c & roll(c, -d, axis=0)) (along a column), periodic.  What
+    spgg_correlations counts on the device, and the path of lattices above its supported side
+    (spgg_correlations_max_side)."""
+    c = (np.asarray(S).astype(np.int64) & 1) == 0
+    L = c.shape[0]
+    D = L // 2 if max_d is None else int(max_d)
+    if c.shape != (L, L) or D < 0 or D > L // 2:
+        raise ValueError(f"host_pair_counts: a square lattice and 0 <= max_d <= L // 2, got {c.shape}, {max_d}")
+    out = np.empty((2, D + 1), dtype=np.int64)
+    for d in range(D + 1):
+        out[0, d] = np.count_nonzero(c & np.roll(c, -d, axis=1))
+        out[1, d] = np.count_nonzero(c & np.roll(c, -d, axis=0))
+    return out
+
+
+def correlation_function(rows, cols, n):
+    """Connected two-point function of the cooperator field from pair counts (any leading axes,
+    the distance last): G(d) = (rows + cols) / (2 n) - (rows[..., 0] / n)^2, n = L * L cells --
+    the direction-averaged <c(x) c(x + d)> minus the squared cooperation rate."""
+    rows, cols = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
+    rho = rows[..., :1] / n
+    return (rows + cols) / (2.0 * n) - rho * rho
+
+
+def correlation_length(G) -> float:
+    """Distance at which g = G / G[0] first falls to 1/e: the first d >= 1 with g(d) <= 1/e,
+    linearly interpolated between d - 1 and d.  nan if G[0] == 0 (an absorbed lattice), inf if g
+    never falls that far within the given distances."""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 1 or G.size == 0:
+        raise ValueError("correlation_length: a one-dimensional G(d), d = 0 ..")
+    if G[0] == 0:
+        return float("nan")
+    g = G / G[0]
+    below = np.nonzero(g[1:] <= 1.0 / np.e)[0]
+    if below.size == 0:
+        return float("inf")
+    d = int(below[0]) + 1
+    return float(d - 1 + (g[d - 1] - 1.0 / np.e) / (g[d - 1] - g[d]))
+
+
 # Library-made streams (spgg_stream_create) are pooled per library and device and outlive their
 # engine: torch's pinned-memory allocator keeps the events of a pinned buffer's copies (run()'s
 # stop flags) and queries them when it allocates again, so a stream destroyed under such an event
@@ -354,6 +398,8 @@ class BatchEngine:
         self._flushed = False
         self._cl_cache = {}        # periodic -> per-replica final cluster sizes (until the next step)
         self.cl_every, self.cl_periodic, self.cl_rec = 0, False, None   # in-run record (run)
+        self._co_cache = {}        # max_d -> (R, 2, max_d + 1) final pair counts (until the next step)
+        self.co_every, self.co_max_d, self.co_rec = 0, 0, None   # in-run pair-count record (run)
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -503,6 +549,9 @@ class BatchEngine:
         side = ctypes.c_int32()
         C.check(self.lib.spgg_clusters_max_side(self.ctx, ctypes.byref(side)), self.ctx, "spgg_clusters_max_side")
         self.clusters_max_side = int(side.value)   # device labelling up to this lattice side
+        C.check(self.lib.spgg_correlations_max_side(self.ctx, ctypes.byref(side)), self.ctx,
+                "spgg_correlations_max_side")
+        self.correlations_max_side = int(side.value)   # device pair counts up to this lattice side
 
     def _draw_layout(self, ctx):
         """(ring slots, u32 words per replica and slot, key-snapshot slots) of the draw records."""
@@ -633,6 +682,7 @@ class BatchEngine:
         if n_steps <= 0:
             return 0
         self._cl_cache = {}
+        self._co_cache = {}
         if self.rng == "inject":
             for _ in range(n_steps):
                 self._inject(self.t)
@@ -718,7 +768,8 @@ class BatchEngine:
 
     def run(self, chunk: int = 256, snapshots: bool = True, png: bool = False,
             progress: Optional[Callable[[int], None]] = None, clusters_every: int = 0,
-            clusters_periodic: bool = False):
+            clusters_periodic: bool = False, correlations_every: int = 0,
+            correlations_max_d: Optional[int] = None):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -734,10 +785,26 @@ class BatchEngine:
         t = 1, 1+k, 1+2k, ... on each replica group's own stream between the step launches of
         t-1 and t (a turn boundary there, no host sync; the stop-flag copies stay `chunk`
         iterations apart); read it with cluster_histories().  With 0 nothing else is enqueued
-        than before."""
+        than before.
+
+        correlations_every = k > 0: the cooperator pair counts of S_t (spgg_correlations) at the
+        distances 0 .. correlations_max_d (None: L // 2) are recorded at t = t0, t0+k, ... (t0
+        the iteration the run starts at) in the same way, and together with the cluster record
+        if both are set; read them with correlation_histories().  The record holds one row per
+        recorded iteration.  With 0 nothing else is enqueued than before."""
         every = int(clusters_every)
         if every < 0:
             raise ValueError("clusters_every must be >= 0")
+        co_every = int(correlations_every)
+        if co_every < 0:
+            raise ValueError("correlations_every must be >= 0")
+        co_d = self.L // 2 if correlations_max_d is None else int(correlations_max_d)
+        if co_every and not 0 <= co_d <= self.L // 2:
+            raise ValueError(f"correlations_max_d must lie in 0 .. L // 2 = {self.L // 2}, got {co_d}")
+        if co_every and self.L > self.correlations_max_side:
+            raise ValueError(f"correlations_every: the device counts lattices up to side "
+                             f"{self.correlations_max_side}, L = {self.L} (count snapshots on the host: "
+                             f"engine.host_pair_counts)")
         if every and self.L > self.clusters_max_side:
             raise ValueError(f"clusters_every: the device labels lattices up to side {self.clusters_max_side}, "
                              f"L = {self.L} (label snapshots on the host: engine.host_cluster_sizes)")
@@ -745,6 +812,11 @@ class BatchEngine:
             # a run continued with the same settings keeps its record and its iterations
             self.cl_rec = torch.zeros((self.R, self.T + 2, 3), dtype=torch.int32, device=self.dev)
             self.cl_every, self.cl_periodic, self._cl_t0 = every, bool(clusters_periodic), self.t
+        if co_every and (self.co_rec is None or (co_every, co_d) != (self.co_every, self.co_max_d)):
+            # one row per recorded iteration t0, t0 + k, ... <= T (a continued run keeps its record)
+            rows = max(1, (self.T - self.t) // co_every + 1)
+            self.co_rec = torch.zeros((self.R, rows, 2 * (co_d + 1)), dtype=torch.int32, device=self.dev)
+            self.co_every, self.co_max_d, self._co_t0 = co_every, co_d, self.t
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -758,11 +830,14 @@ class BatchEngine:
         turn = 0
         done = False
         t_rec0 = self._cl_t0 if every else 0   # the record's iterations: t_rec0, t_rec0 + every, ...
+        t_co0 = self._co_t0 if co_every else 0
         check_at = self.t + chunk  # the stop flags are copied every `chunk` iterations and at stops
         with torch.cuda.stream(loop):
             while self.t <= self.T and not done:
                 if every and (self.t - t_rec0) % every == 0:
                     self._record_clusters(self.t)
+                if co_every and (self.t - t_co0) % co_every == 0:
+                    self._record_correlations(self.t)
                 if self.t in stops:
                     self._capture(self.t, snapshots and self.t in SNAPSHOT_ITERS,
                                   png and (self.t - 1) in PNG_ITERS)
@@ -773,11 +848,13 @@ class BatchEngine:
                 nxt = min([s for s in stops if s > self.t] + [check_at, self.T + 1])
                 if every:
                     nxt = min(nxt, self.t + every - (self.t - t_rec0) % every)
+                if co_every:
+                    nxt = min(nxt, self.t + co_every - (self.t - t_co0) % co_every)
                 self.step(nxt - self.t)
                 if progress:
                     progress(self.t - 1)
                 if self.t < check_at and self.t <= self.T and self.t not in stops:
-                    continue       # a turn boundary of the cluster record only
+                    continue       # a turn boundary of the cluster / pair-count record only
                 check_at = self.t + chunk
                 slot, turn = turn & 1, turn + 1
                 flags[slot].copy_(self.stop_iter, non_blocking=True)
@@ -910,6 +987,57 @@ class BatchEngine:
                                   f"({C.CLUSTERS_MAX_PASSES}) at iterations {its[r[:, 0] < 0].tolist()}")
             out.append(dict(cluster_history_iters=its, cluster_count_history=r[:, 0].copy(),
                             largest_cluster_history=r[:, 1].copy(), cd_bond_history=r[:, 2].copy()))
+        return out
+
+    # -- pair correlations ---------------------------------------------------
+    def _correlations(self, t, max_d, out, row, stride):
+        """Enqueue spgg_correlations of S_t on every group's stream: replica k's 2 * (max_d + 1)
+        counts into out.view(-1)[k * stride + row:] (row, stride in int32)."""
+        def one(g, s):
+            C.check(self.lib.spgg_correlations(
+                g["ctx"], int(t), int(max_d), out.data_ptr() + 4 * (g["r0"] * stride + row), stride, s),
+                g["ctx"], "spgg_correlations")
+        self._enqueue(one)
+
+    def _record_correlations(self, t):
+        """The in-run record of S_t into its row of co_rec (run(correlations_every=...))."""
+        width = 2 * (self.co_max_d + 1)
+        self._correlations(t, self.co_max_d, self.co_rec, (t - self._co_t0) // self.co_every * width,
+                           self.co_rec.shape[1] * width)
+
+    def pair_counts(self, k, max_d: Optional[int] = None) -> np.ndarray:
+        """int64 (2, D+1) cooperator pair counts of replica k in the state final_state(k) returns,
+        D = max_d (None: L // 2): [0, d] pairs d apart along a row, [1, d] along a column, on the
+        periodic lattice ([0, 0] = [1, 0] = the number of cooperators).  Counted on the device, all
+        replicas at once (one spgg_correlations launch per replica group) and cached until the
+        engine steps again; lattices above the supported side are counted on the host, same
+        result.  correlation_function / correlation_length turn the counts into G(d) and xi."""
+        D = self.L // 2 if max_d is None else int(max_d)
+        if not 0 <= D <= self.L // 2:
+            raise ValueError(f"pair_counts: max_d must lie in 0 .. L // 2 = {self.L // 2}, got {max_d}")
+        if self.L > self.correlations_max_side:
+            return host_pair_counts(self.final_state(k)[2], D)
+        if D not in self._co_cache:
+            out = torch.empty((self.R, 2 * (D + 1)), dtype=torch.int32, device=self.dev)
+            self._correlations(self.t, D, out, 0, 2 * (D + 1))
+            self._co_cache[D] = out.cpu().numpy().astype(np.int64).reshape(self.R, 2, D + 1)
+        return self._co_cache[D][k].copy()
+
+    def correlation_histories(self):
+        """Per replica, the in-run pair-count record of run(correlations_every=k):
+        correlation_history_iters (the recorded iterations t <= last_iteration, so a replica
+        absorbed at s keeps the record of S_s if s was recorded), pair_count_rows_history and
+        pair_count_cols_history, int64 (m, D+1)."""
+        if not self.co_every or self.co_rec is None:
+            raise ValueError("correlation_histories: run(correlations_every=k) with k > 0 first")
+        D = self.co_max_d
+        rec = self.co_rec.cpu().numpy().astype(np.int64)
+        out = []
+        for k in range(self.R):
+            its = np.arange(self._co_t0, self.last_iteration(k) + 1, self.co_every, dtype=np.int64)
+            r = rec[k, :len(its)]
+            out.append(dict(correlation_history_iters=its, pair_count_rows_history=r[:, :D + 1].copy(),
+                            pair_count_cols_history=r[:, D + 1:].copy()))
         return out
 
     def finalize_history(self):

@@ -38,6 +38,11 @@ class SPGG:
     # cluster_history_periodic (the final cluster_sizes dataset never does: spgg.py:631).
     cluster_history_every = 0
     cluster_history_periodic = False
+    # k > 0: also record the cooperator pair counts of S_t along rows and columns at the
+    # distances 0 .. correlation_max_distance (None: L // 2) at t = 1, 1+k, ... on the device and
+    # write them as three more datasets (CORRELATION_DATASETS); 0: the reference's file.
+    correlation_history_every = 0
+    correlation_max_distance = None
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -145,11 +150,14 @@ class SPGG:
         os.makedirs(snapshots_dir, exist_ok=True)
         try:
             every = int(self.cluster_history_every or 0)
+            co_every = int(self.correlation_history_every or 0)
             eng.run(snapshots=True, png=self.save_png, clusters_every=every,
-                    clusters_periodic=bool(self.cluster_history_periodic))
+                    clusters_periodic=bool(self.cluster_history_periodic), correlations_every=co_every,
+                    correlations_max_d=self.correlation_max_distance)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (host above its supported side)
             cluster_hist = eng.cluster_histories()[0] if every > 0 else None
+            correlation_hist = eng.correlation_histories()[0] if co_every > 0 else None
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -180,7 +188,7 @@ class SPGG:
         # the datasets last: the reference fills its file after the loop, so a write
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
-                       clusters=clusters, cluster_hist=cluster_hist)
+                       clusters=clusters, cluster_hist=cluster_hist, correlation_hist=correlation_hist)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -199,15 +207,20 @@ CLUSTER_DATASETS = ("cluster_history_iters", "cluster_count_history", "largest_c
                     "cd_bond_history")
 
 
+CORRELATION_DATASETS = ("correlation_history_iters", "pair_count_rows_history", "pair_count_cols_history")
+
+
 def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
-                   cluster_hist=None):
+                   cluster_hist=None, correlation_hist=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
     the final state.  Shared by SPGG.run and the batched sweep runner.
 
     clusters: the final cluster sizes (BatchEngine.cluster_sizes) instead of labelling S on the
     host here; cluster_hist: the in-run cluster record (BatchEngine.cluster_histories), written
-    as the CLUSTER_DATASETS after the reference's own.  The defaults write the reference's file."""
+    as the CLUSTER_DATASETS after the reference's own; correlation_hist: the in-run pair-count
+    record (BatchEngine.correlation_histories), written as the CORRELATION_DATASETS after those.
+    The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
             Ri, Si = snaps[i]
@@ -242,6 +255,9 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
         if cluster_hist is not None:
             for name in CLUSTER_DATASETS:
                 data_file.create_dataset(name, data=np.asarray(cluster_hist[name], dtype=np.int64))
+        if correlation_hist is not None:
+            for name in CORRELATION_DATASETS:
+                data_file.create_dataset(name, data=np.asarray(correlation_hist[name], dtype=np.int64))
 
 
 def track_positions(L):

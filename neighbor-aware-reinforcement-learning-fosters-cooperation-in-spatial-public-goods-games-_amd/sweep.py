@@ -190,11 +190,14 @@ def run_one_experiment(params: Tuple, **model_overrides) -> Tuple[Tuple, Tuple[f
     kw = dict(RUNNER_MODEL, **model_overrides)
     every = int(kw.pop("cluster_history_every", 0) or 0)   # class attributes of the drop-in,
     periodic = bool(kw.pop("cluster_history_periodic", False))   # not constructor arguments
+    co_every = int(kw.pop("correlation_history_every", 0) or 0)
+    co_max_d = kw.pop("correlation_max_distance", None)
     spgg = SPGG(r=r, alpha=alpha, influence_factor=kappa, use_second_order=so,
                 reward_weight_payoff=w_p, rep_gain_C=gain, state_representation=state,
                 algorithm=algorithm, **kw)
     spgg.folder = folder
     spgg.cluster_history_every, spgg.cluster_history_periodic = every, periodic
+    spgg.correlation_history_every, spgg.correlation_max_distance = co_every, co_max_d
     coop, _def, _p = spgg.run(os.path.join(folder, "data", "experiment_data.h5"))
     rep_mean = spgg.rep_avg_history[-1] if spgg.rep_avg_history else 0
     print(_done_line(p8))
@@ -230,6 +233,9 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
     # the in-run cluster record (SPGG.cluster_history_every / _periodic): not constructor arguments
     every = int(kw.pop("cluster_history_every", 0) or 0)
     periodic = bool(kw.pop("cluster_history_periodic", False))
+    # the in-run pair-count record (SPGG.correlation_history_every / correlation_max_distance)
+    co_every = int(kw.pop("correlation_history_every", 0) or 0)
+    co_max_d = kw.pop("correlation_max_distance", None)
     L, iters = int(kw["L"]), int(kw["iterations"])
     p8s = [unpack(p) for p in param_list]
     seeds = list(seeds) if seeds is not None else [None] * len(p8s)
@@ -253,16 +259,18 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
                           rng="mt19937", init=inits, algorithm=alg)
         try:
             eng.run(snapshots=True, png=save_png, progress=progress, clusters_every=every,
-                    clusters_periodic=periodic)
+                    clusters_periodic=periodic, correlations_every=co_every, correlations_max_d=co_max_d)
             hist = eng.histories()
             cl_hist = eng.cluster_histories() if every > 0 else None
+            co_hist = eng.correlation_histories() if co_every > 0 else None
             for k, i in enumerate(idx):
                 folder = get_folder_name(*p8s[i])
                 make_folders(folder)
                 _q, R, S = eng.final_state(k)
                 write_datasets(os.path.join(folder, "data", "experiment_data.h5"), hist[k], eng.snapshots[k],
                                S, R, kw["R_min"], kw["R_max"], track_positions(L),
-                               clusters=eng.cluster_sizes(k), cluster_hist=cl_hist[k] if cl_hist else None)
+                               clusters=eng.cluster_sizes(k), cluster_hist=cl_hist[k] if cl_hist else None,
+                               correlation_hist=co_hist[k] if co_hist else None)
                 if save_png and eng.png_frames[k]:
                     _write_pngs(eng.png_frames[k], os.path.join(folder, "plots", "snapshots"))
                 coop = float(np.sum(S == 0)) / (L * L)
