@@ -15,7 +15,8 @@ Random streams:
     further selects and Double-Q's table choice -- bit-identically.
   * "inject": the host draws each step (tests / debugging).
   * "philox": counter-based Philox2x32-10 stream (one block per agent pair and
-    iteration); statistical parity only.
+    iteration; the contract is in spgg_abi.h): bit-exact against the oracle fed
+    the same draws, statistical parity with the reference's MT19937 stream.
 """
 from __future__ import annotations
 

@@ -46,6 +46,11 @@ def test_dump_is_the_engines_final_state_and_repeats(tmp_path, capsys):
     assert np.array_equal(a["stop_iter"], np.zeros(8))
     assert np.array_equal(a["coop_trace"], ncoop[:, 4:8] / (L * L))     # iterations 4-7
     assert abs(a["coop_final"].mean() - line["gather"]["mean_final_coop"]) < 1e-15
+    # and the dump is the oracle's state under the same Philox draws (oracle/philox.py)
+    from tests._philox import check_final, philox_oracle
+    for k in (0, 7):
+        _, want = philox_oracle(L, 7, reps[k], k, M2, state)
+        check_final((a["Q"][k], a["R"][k], a["S"][k]), want, k)
 
 
 def test_large_outputs_are_a_fixed_sample(tmp_path, capsys):

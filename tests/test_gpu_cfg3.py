@@ -14,6 +14,7 @@ import bench  # noqa: E402  (repository root)
 import spgg_amd  # noqa: E402
 from spgg_amd.engine import BatchEngine  # noqa: E402
 from oracle import spgg_oracle as O  # noqa: E402
+from tests._philox import check_replica, philox_oracle  # noqa: E402
 
 FLOAT_TOL = dict(rtol=1e-5, atol=1e-9)
 T = 20
@@ -58,6 +59,28 @@ def test_cfg3_batch_mt19937_vs_oracle():
                 np.testing.assert_allclose(hs[k][key], ds[key], equal_nan=True, err_msg=f"{k} {key}",
                                            **FLOAT_TOL)
             if p.influence_factor == 0.0:   # the kappa == 0 record skip: the NI share is exactly 0
+                assert np.all(hs[k]["neighbor_influence_percent"] == 0.0), k
+    finally:
+        eng.close()
+
+
+def test_cfg3_batch_philox_vs_oracle():
+    """The bench's workload in the bench's own stream and planned layout, against the oracle
+    under the same counter-based draws (oracle/philox.py): the cells of the MT19937 test, every
+    replica's stream keyed by its index in the batch."""
+    _, L, M2, state, reps = bench.workload("cfg3", 0)
+    eng = BatchEngine(L, T, reps, use_second_order=M2, state_representation=state, rng="philox")
+    try:
+        assert eng.G == 2 and eng.waves == 1, (eng.G, eng.waves)      # the bench's plan
+        assert eng.tile == (40, 25)                                     # TWC=40 kernel instance
+        eng.run(snapshots=False)
+        hs = eng.histories()
+        cells = [i * 15 + j * 5 + (i + j) % 5 for i in range(7) for j in range(3)]
+        assert {k < eng.groups[0]["r1"] for k in cells} == {True, False}   # both replica groups
+        for k in cells:
+            ds, fin = philox_oracle(L, T, reps[k], k, M2, state)
+            check_replica(eng, hs[k], k, ds, fin)
+            if reps[k].influence_factor == 0.0:
                 assert np.all(hs[k]["neighbor_influence_percent"] == 0.0), k
     finally:
         eng.close()

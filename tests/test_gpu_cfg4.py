@@ -94,6 +94,33 @@ def test_cfg4_workload_bit_exact_vs_oracle(monkeypatch):
         assert np.array_equal(keys[k][0], np.asarray(st[1], dtype=np.uint32)) and keys[k][1] == st[2], k
 
 
+def test_cfg4_workload_philox_bit_exact_vs_oracle(monkeypatch):
+    """The same workload and planned layout in the bench's own stream (rng="philox"), against the
+    oracle under the same counter-based draws (oracle/philox.py): two of the eight replicas, one
+    from each replica group."""
+    import multiprocessing as mp
+    from tests._philox import check_replica, param_dict, philox_oracle_job
+    for k in OVERRIDES:
+        monkeypatch.delenv(k, raising=False)
+    L, T = 200, 100
+    reps = [runner_params(seed=s) for s in range(8)]
+    checked = (1, 6)
+    jobs = [(L, T, param_dict(reps[k]), reps[k].seed, k, True, "action") for k in checked]
+    with mp.get_context("spawn").Pool(len(jobs)) as pool:
+        pending = pool.map_async(philox_oracle_job, jobs)      # the oracle runs beside the device run
+        eng = BatchEngine(L, T, reps, use_second_order=True, state_representation="action", rng="philox")
+        try:
+            assert eng.tile == (20, 25) and eng.G == 2, (eng.tile, eng.G)
+            assert [k < eng.groups[0]["r1"] for k in checked] == [True, False]
+            eng.run(snapshots=False)
+            hist = eng.histories()
+            want = pending.get()
+            for k, (ds, fin) in zip(checked, want):
+                check_replica(eng, hist[k], k, ds, fin)
+        finally:
+            eng.close()
+
+
 def test_run_sharded_mean_P_matches_oracle():
     """run_sharded's summaries (distributed.replica_summaries): final rates, mean_P -- the mean
     payoff of the last iteration a replica started, SPGG.run's third return value
