@@ -13,7 +13,7 @@ import threading
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libspgg_hip.so")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 OK, E_ARG, E_STATE, E_HIP = 0, -1, -2, -3
 GEN_ERR_SPIN = 1
 CLUSTERS_MAX_PASSES = 32   # SPGG_CLUSTERS_MAX_PASSES (spgg_abi.h): pass cap of spgg_clusters
@@ -39,7 +39,8 @@ EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create
             "spgg_history_finalize", "spgg_draw_layout", "spgg_set_draw_stream", "spgg_draw_range",
             "spgg_mt_chains", "spgg_mt_jump_poly", "spgg_stream_create", "spgg_stream_destroy",
             "spgg_status", "spgg_persistent", "spgg_clusters", "spgg_clusters_max_side",
-            "spgg_correlations", "spgg_correlations_max_side")
+            "spgg_correlations", "spgg_correlations_max_side", "spgg_reputation_hist",
+            "spgg_reputation_pairs", "spgg_reputation_max_side")
 # test-only entry points (include/spgg_test.h): exported by the library, not part of the product ABI
 TEST_EXPORTED = ("spgg_test_set_error",)
 
@@ -127,6 +128,12 @@ def load(path: str | None = None):
         lib.spgg_correlations.argtypes = [vp, i32, i32, vp, ctypes.c_int64, vp]
         lib.spgg_correlations_max_side.restype = ctypes.c_int
         lib.spgg_correlations_max_side.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.spgg_reputation_hist.restype = ctypes.c_int
+        lib.spgg_reputation_hist.argtypes = [vp, i32, i32, vp, vp, ctypes.c_int64, vp]
+        lib.spgg_reputation_pairs.restype = ctypes.c_int
+        lib.spgg_reputation_pairs.argtypes = [vp, i32, i32, vp, ctypes.c_int64, vp]
+        lib.spgg_reputation_max_side.restype = ctypes.c_int
+        lib.spgg_reputation_max_side.argtypes = [vp, ctypes.POINTER(i32)]
         lib.spgg_persistent.restype = ctypes.c_int
         lib.spgg_persistent.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         lib.spgg_destroy.restype = ctypes.c_int

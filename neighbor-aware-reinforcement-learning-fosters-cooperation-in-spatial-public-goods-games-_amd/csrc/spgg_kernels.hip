@@ -46,6 +46,7 @@
 #include "spgg_mt.h"
 #include "spgg_clusters.h"
 #include "spgg_correlations.h"
+#include "spgg_reputation.h"
 
 using namespace spgg;
 
@@ -3623,6 +3624,49 @@ int spgg_correlations(spgg_ctx* c, int32_t t, int32_t max_d, int32_t* out, int64
   spgg_co::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, max_d, out, out_stride,
                   reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_correlations launch");
+}
+
+int spgg_reputation_max_side(const spgg_ctx* c, int32_t* side) {
+  if (!c || !side) return SPGG_E_ARG;
+  *side = spgg_rp::kMaxSide;
+  return SPGG_OK;
+}
+
+int spgg_reputation_hist(spgg_ctx* c, int32_t t, int32_t bins, const double* edges, int32_t* out, int64_t out_stride,
+                         void* stream) {
+  if (!c || !edges || !out) return fail(c, SPGG_E_ARG, "null argument");
+  if (!c->bound || !c->params_set) return fail(c, SPGG_E_STATE, "spgg_reputation_hist before bind/set_params");
+  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_reputation_hist: bad t");
+  if (bins < 1 || bins > spgg_rp::kMaxBins)
+    return fail(c, SPGG_E_ARG, "spgg_reputation_hist: bins = " + std::to_string(bins) + " outside 1 .. " +
+                                   std::to_string(spgg_rp::kMaxBins));
+  if (out_stride < 2 * (int64_t)bins)
+    return fail(c, SPGG_E_ARG, "spgg_reputation_hist: out_stride below 2 * bins");
+  spgg_rp::launch_hist(c->buf.S[0], c->buf.S[1], c->buf.R[0], c->buf.R[1], c->cfg.rep_int8 != 0, c->d_params,
+                       c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, bins, edges, out, out_stride,
+                       reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_reputation_hist launch");
+}
+
+int spgg_reputation_pairs(spgg_ctx* c, int32_t t, int32_t max_d, int64_t* out, int64_t out_stride, void* stream) {
+  if (!c || !out) return fail(c, SPGG_E_ARG, "null argument");
+  if (!c->bound) return fail(c, SPGG_E_STATE, "spgg_reputation_pairs before bind");
+  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: bad t");
+  if (!c->cfg.rep_int8)
+    return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: the reputation buffers hold f64 (rep_int8 = 0); the pair sums "
+                               "are exact integers of the int8 path only");
+  if (c->cfg.L > spgg_rp::kMaxSide)
+    return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: L = " + std::to_string(c->cfg.L) + " exceeds the supported side " +
+                                   std::to_string(spgg_rp::kMaxSide) + " (int32 lane partials)");
+  if (max_d < 0 || max_d > c->cfg.L / 2)
+    return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: max_d = " + std::to_string(max_d) + " outside 0 .. L / 2 = " +
+                                   std::to_string(c->cfg.L / 2));
+  if (out_stride < 2 * (int64_t)(max_d + 1) + 1)
+    return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: out_stride below 2 * (max_d + 1) + 1");
+  spgg_rp::launch_pairs(static_cast<const int8_t*>(c->buf.R[0]), static_cast<const int8_t*>(c->buf.R[1]),
+                        c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, max_d, reinterpret_cast<long long*>(out), out_stride,
+                        reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_reputation_pairs launch");
 }
 
 int spgg_status(const spgg_ctx* c, uint32_t* flags) {

@@ -287,6 +287,42 @@ def correlation_length(G) -> float:
     return float(d - 1 + (g[d - 1] - 1.0 / np.e) / (g[d - 1] - g[d]))
 
 
+def reputation_bin_edges(R_min, R_max, bins: int = 20) -> np.ndarray:
+    """The bins + 1 edges np.histogram(x, bins=bins, range=(R_min, R_max)) uses -- with bins = 20
+    the reference's rep_bins_* datasets (spgg.py:399)."""
+    return np.histogram_bin_edges(np.empty(0), int(bins), (float(R_min), float(R_max)))
+
+
+def host_reputation_pair_sums(K, max_d=None):
+    """(sum, rows, cols) of one reputation lattice on the host, D = max_d (None: L // 2): sum =
+    K.sum(), rows[d] = sum(K * roll(K, -d, axis=1)), cols[d] = sum(K * roll(K, -d, axis=0)) for
+    d = 0 .. D, periodic.  Integer input (the int8 plane, in units of rep_unit) is summed in int64
+    and is what spgg_reputation_pairs gives on the device, exactly; float input (R itself, the f64
+    reputation path) gives the same sums in float64, rounded and so not exact.  The path of
+    f64-reputation engines and of lattices above spgg_reputation_max_side."""
+    K = np.asarray(K)
+    L = K.shape[0]
+    D = L // 2 if max_d is None else int(max_d)
+    if K.shape != (L, L) or D < 0 or D > L // 2:
+        raise ValueError(f"host_reputation_pair_sums: a square lattice and 0 <= max_d <= L // 2, got {K.shape}, {max_d}")
+    K = K.astype(np.int64 if np.issubdtype(K.dtype, np.integer) else np.float64)
+    rows, cols = np.empty(D + 1, dtype=K.dtype), np.empty(D + 1, dtype=K.dtype)
+    for d in range(D + 1):
+        rows[d] = np.sum(K * np.roll(K, -d, axis=1))
+        cols[d] = np.sum(K * np.roll(K, -d, axis=0))
+    return K.sum(), rows, cols
+
+
+def reputation_correlation_function(sum, rows, cols, n, unit):
+    """Connected two-point function of the reputation field from pair sums (any leading axes, the
+    distance last; sum without the distance axis): unit^2 * ((rows + cols) / (2 n) - (sum / n)^2),
+    n = L * L cells, unit the replica's rep_unit (1 for sums of R itself) -- the direction-averaged
+    <R(x) R(x + d)> minus the squared mean.  correlation_length applies to it as it stands."""
+    rows, cols = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
+    mean = np.asarray(sum, dtype=np.float64)[..., None] / n
+    return float(unit) ** 2 * ((rows + cols) / (2.0 * n) - mean * mean)
+
+
 # Library-made streams (spgg_stream_create) are pooled per library and device and outlive their
 # engine: torch's pinned-memory allocator keeps the events of a pinned buffer's copies (run()'s
 # stop flags) and queries them when it allocates again, so a stream destroyed under such an event
@@ -401,6 +437,9 @@ class BatchEngine:
         self.cl_every, self.cl_periodic, self.cl_rec = 0, False, None   # in-run record (run)
         self._co_cache = {}        # max_d -> (R, 2, max_d + 1) final pair counts (until the next step)
         self.co_every, self.co_max_d, self.co_rec = 0, 0, None   # in-run pair-count record (run)
+        self._rp_cache = {}        # final reputation histograms / pair sums (until the next step)
+        self.rp_every, self.rp_bins, self.rp_max_d = 0, 0, None   # in-run reputation record (run)
+        self.rp_hist_rec = self.rp_pair_rec = self.rp_edges = None
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -553,6 +592,9 @@ class BatchEngine:
         C.check(self.lib.spgg_correlations_max_side(self.ctx, ctypes.byref(side)), self.ctx,
                 "spgg_correlations_max_side")
         self.correlations_max_side = int(side.value)   # device pair counts up to this lattice side
+        C.check(self.lib.spgg_reputation_max_side(self.ctx, ctypes.byref(side)), self.ctx,
+                "spgg_reputation_max_side")
+        self.reputation_max_side = int(side.value)   # device reputation pair sums up to this lattice side
 
     def _draw_layout(self, ctx):
         """(ring slots, u32 words per replica and slot, key-snapshot slots) of the draw records."""
@@ -684,6 +726,7 @@ class BatchEngine:
             return 0
         self._cl_cache = {}
         self._co_cache = {}
+        self._rp_cache = {}
         if self.rng == "inject":
             for _ in range(n_steps):
                 self._inject(self.t)
@@ -770,7 +813,8 @@ class BatchEngine:
     def run(self, chunk: int = 256, snapshots: bool = True, png: bool = False,
             progress: Optional[Callable[[int], None]] = None, clusters_every: int = 0,
             clusters_periodic: bool = False, correlations_every: int = 0,
-            correlations_max_d: Optional[int] = None):
+            correlations_max_d: Optional[int] = None, reputation_every: int = 0,
+            reputation_bins: int = 20, reputation_max_d: Optional[int] = None):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -792,7 +836,32 @@ class BatchEngine:
         distances 0 .. correlations_max_d (None: L // 2) are recorded at t = t0, t0+k, ... (t0
         the iteration the run starts at) in the same way, and together with the cluster record
         if both are set; read them with correlation_histories().  The record holds one row per
-        recorded iteration.  With 0 nothing else is enqueued than before."""
+        recorded iteration.  With 0 nothing else is enqueued than before.
+
+        reputation_every = k > 0: the joint histogram strategy x reputation bin of (S_t, R_t)
+        (spgg_reputation_hist; reputation_bins bins over each replica's R_min .. R_max, the
+        reference's edges) is recorded at t = t0, t0+k, ... in the same way, beside the other two
+        records; with reputation_max_d not None also the pair sums of the int8 reputation plane
+        (spgg_reputation_pairs) at the distances 0 .. reputation_max_d -- a ValueError on an
+        f64-reputation engine or above reputation_max_side, before anything is enqueued.  Read
+        them with reputation_histories().  With 0 nothing else is enqueued than before."""
+        rp_every = int(reputation_every)
+        if rp_every < 0:
+            raise ValueError("reputation_every must be >= 0")
+        rp_bins = int(reputation_bins)
+        rp_d = None if reputation_max_d is None else int(reputation_max_d)
+        if rp_every and not 1 <= rp_bins <= 256:
+            raise ValueError(f"reputation_bins must lie in 1 .. 256, got {rp_bins}")
+        if rp_every and rp_d is not None:
+            if not self.rep_int8:
+                raise ValueError("reputation_max_d: the pair sums are exact integers of the int8 reputation path; "
+                                 "this engine holds f64 reputation (non-dyadic gains or bounds) -- sum snapshots "
+                                 "on the host: engine.host_reputation_pair_sums")
+            if self.L > self.reputation_max_side:
+                raise ValueError(f"reputation_max_d: the device sums lattices up to side {self.reputation_max_side}, "
+                                 f"L = {self.L} (sum snapshots on the host: engine.host_reputation_pair_sums)")
+            if not 0 <= rp_d <= self.L // 2:
+                raise ValueError(f"reputation_max_d must lie in 0 .. L // 2 = {self.L // 2}, got {rp_d}")
         every = int(clusters_every)
         if every < 0:
             raise ValueError("clusters_every must be >= 0")
@@ -818,6 +887,13 @@ class BatchEngine:
             rows = max(1, (self.T - self.t) // co_every + 1)
             self.co_rec = torch.zeros((self.R, rows, 2 * (co_d + 1)), dtype=torch.int32, device=self.dev)
             self.co_every, self.co_max_d, self._co_t0 = co_every, co_d, self.t
+        if rp_every and (self.rp_hist_rec is None or (rp_every, rp_bins, rp_d) != (self.rp_every, self.rp_bins, self.rp_max_d)):
+            rows = max(1, (self.T - self.t) // rp_every + 1)
+            self.rp_hist_rec = torch.zeros((self.R, rows, 2 * rp_bins), dtype=torch.int32, device=self.dev)
+            self.rp_pair_rec = (None if rp_d is None else
+                                torch.zeros((self.R, rows, 2 * (rp_d + 1) + 1), dtype=torch.int64, device=self.dev))
+            self.rp_edges = self._reputation_edges(rp_bins)
+            self.rp_every, self.rp_bins, self.rp_max_d, self._rp_t0 = rp_every, rp_bins, rp_d, self.t
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -832,6 +908,7 @@ class BatchEngine:
         done = False
         t_rec0 = self._cl_t0 if every else 0   # the record's iterations: t_rec0, t_rec0 + every, ...
         t_co0 = self._co_t0 if co_every else 0
+        t_rp0 = self._rp_t0 if rp_every else 0
         check_at = self.t + chunk  # the stop flags are copied every `chunk` iterations and at stops
         with torch.cuda.stream(loop):
             while self.t <= self.T and not done:
@@ -839,6 +916,8 @@ class BatchEngine:
                     self._record_clusters(self.t)
                 if co_every and (self.t - t_co0) % co_every == 0:
                     self._record_correlations(self.t)
+                if rp_every and (self.t - t_rp0) % rp_every == 0:
+                    self._record_reputation(self.t)
                 if self.t in stops:
                     self._capture(self.t, snapshots and self.t in SNAPSHOT_ITERS,
                                   png and (self.t - 1) in PNG_ITERS)
@@ -851,11 +930,13 @@ class BatchEngine:
                     nxt = min(nxt, self.t + every - (self.t - t_rec0) % every)
                 if co_every:
                     nxt = min(nxt, self.t + co_every - (self.t - t_co0) % co_every)
+                if rp_every:
+                    nxt = min(nxt, self.t + rp_every - (self.t - t_rp0) % rp_every)
                 self.step(nxt - self.t)
                 if progress:
                     progress(self.t - 1)
                 if self.t < check_at and self.t <= self.T and self.t not in stops:
-                    continue       # a turn boundary of the cluster / pair-count record only
+                    continue       # a turn boundary of the cluster / pair-count / reputation record only
                 check_at = self.t + chunk
                 slot, turn = turn & 1, turn + 1
                 flags[slot].copy_(self.stop_iter, non_blocking=True)
@@ -1039,6 +1120,119 @@ class BatchEngine:
             r = rec[k, :len(its)]
             out.append(dict(correlation_history_iters=its, pair_count_rows_history=r[:, :D + 1].copy(),
                             pair_count_cols_history=r[:, D + 1:].copy()))
+        return out
+
+    # -- reputation record ---------------------------------------------------
+    def _reputation_edges(self, bins, edges=None):
+        """Device f64 (R, bins + 1) edges: each replica's reference edges over its R_min .. R_max,
+        or the given ones for every replica."""
+        if edges is None:
+            e = np.stack([reputation_bin_edges(p.R_min, p.R_max, bins) for p in self.reps])
+        else:
+            e = np.asarray(edges, dtype=np.float64)
+            if e.shape != (bins + 1,) or not np.all(np.diff(e) > 0):
+                raise ValueError(f"reputation edges: {bins + 1} ascending values, got shape {e.shape}")
+            e = np.broadcast_to(e, (self.R, bins + 1))
+        return torch.from_numpy(np.ascontiguousarray(e)).to(self.dev)
+
+    def _reputation_hist(self, t, bins, edges, out, row, stride):
+        """Enqueue spgg_reputation_hist of (S_t, R_t) on every group's stream: replica k's 2 * bins
+        counts into out.view(-1)[k * stride + row:] (row, stride in int32)."""
+        def one(g, s):
+            C.check(self.lib.spgg_reputation_hist(
+                g["ctx"], int(t), int(bins), edges.data_ptr() + 8 * g["r0"] * (bins + 1),
+                out.data_ptr() + 4 * (g["r0"] * stride + row), stride, s), g["ctx"], "spgg_reputation_hist")
+        self._enqueue(one)
+
+    def _reputation_pairs(self, t, max_d, out, row, stride):
+        """Enqueue spgg_reputation_pairs of R_t on every group's stream: replica k's
+        2 * (max_d + 1) + 1 sums into out.view(-1)[k * stride + row:] (row, stride in int64)."""
+        def one(g, s):
+            C.check(self.lib.spgg_reputation_pairs(
+                g["ctx"], int(t), int(max_d), out.data_ptr() + 8 * (g["r0"] * stride + row), stride, s),
+                g["ctx"], "spgg_reputation_pairs")
+        self._enqueue(one)
+
+    def _record_reputation(self, t):
+        """The in-run record of (S_t, R_t) into its row of the records (run(reputation_every=...))."""
+        row = (t - self._rp_t0) // self.rp_every
+        width = 2 * self.rp_bins
+        self._reputation_hist(t, self.rp_bins, self.rp_edges, self.rp_hist_rec, row * width,
+                              self.rp_hist_rec.shape[1] * width)
+        if self.rp_pair_rec is not None:
+            width = 2 * (self.rp_max_d + 1) + 1
+            self._reputation_pairs(t, self.rp_max_d, self.rp_pair_rec, row * width, self.rp_pair_rec.shape[1] * width)
+
+    def reputation_histogram(self, k, bins: int = 20, edges=None) -> np.ndarray:
+        """int64 (2, bins) joint histogram strategy x reputation bin of replica k in the state
+        final_state(k) returns: [0] cooperators, [1] defectors; [0] + [1] with the default edges
+        (the reference's for the replica's R_min .. R_max) is the reference's rep_hist_final.
+        `edges`: bins + 1 ascending values used for every replica instead.  np.histogram's rule
+        (the last bin closed, values outside counted nowhere).  Counted on the device, all replicas
+        at once (one spgg_reputation_hist call per replica group) and cached until the engine
+        steps again."""
+        bins = int(bins)
+        if not 1 <= bins <= 256:
+            raise ValueError(f"reputation_histogram: bins must lie in 1 .. 256, got {bins}")
+        key = ("hist", bins, None if edges is None else np.asarray(edges, dtype=np.float64).tobytes())
+        if key not in self._rp_cache:
+            e = self._reputation_edges(bins, edges)
+            out = torch.empty((self.R, 2 * bins), dtype=torch.int32, device=self.dev)
+            self._reputation_hist(self.t, bins, e, out, 0, 2 * bins)
+            self._rp_cache[key] = out.cpu().numpy().astype(np.int64).reshape(self.R, 2, bins)
+        return self._rp_cache[key][k].copy()
+
+    def reputation_pair_sums(self, k, max_d: Optional[int] = None):
+        """(sum, rows, cols) of replica k's reputation plane in the state final_state(k) returns,
+        D = max_d (None: L // 2): on the int8 path int64 sums of the stored bytes (sum in units of
+        the replica's rep_unit, rows / cols (D+1,) in rep_unit^2: rows[d] the products d apart along
+        a row, cols[d] along a column, periodic), exact; summed on the device, all replicas at once
+        and cached until the engine steps again.  An f64-reputation engine and lattices above
+        reputation_max_side are summed on the host (host_reputation_pair_sums: the f64 engine's
+        are float64 sums of R itself, unit 1, not exact).  reputation_correlation_function turns
+        them into G(d)."""
+        D = self.L // 2 if max_d is None else int(max_d)
+        if not 0 <= D <= self.L // 2:
+            raise ValueError(f"reputation_pair_sums: max_d must lie in 0 .. L // 2 = {self.L // 2}, got {max_d}")
+        if not self.rep_int8:
+            return host_reputation_pair_sums(self.final_state(k)[1], D)
+        if self.L > self.reputation_max_side:
+            s = int(self.stopped[k])
+            cur = (s - 1) & 1 if s else self.last_iteration(k) & 1
+            return host_reputation_pair_sums(self.Rep[cur, k].cpu().numpy().reshape(self.L, self.L), D)
+        key = ("pairs", D)
+        if key not in self._rp_cache:
+            width = 2 * (D + 1) + 1
+            out = torch.empty((self.R, width), dtype=torch.int64, device=self.dev)
+            self._reputation_pairs(self.t, D, out, 0, width)
+            self._rp_cache[key] = out.cpu().numpy()
+        r = self._rp_cache[key][k]
+        return int(r[0]), r[1:D + 2].copy(), r[D + 2:].copy()
+
+    def reputation_histories(self):
+        """Per replica, the in-run reputation record of run(reputation_every=k):
+        reputation_history_iters (the recorded iterations t <= last_iteration),
+        reputation_hist_history int64 (m, 2, bins) and reputation_bin_edges f64 (bins + 1,); with
+        reputation_max_d also reputation_sum_history (m,), reputation_pair_rows_history and
+        reputation_pair_cols_history (m, D+1), int64 in units of reputation_unit (squared)."""
+        if not self.rp_every or self.rp_hist_rec is None:
+            raise ValueError("reputation_histories: run(reputation_every=k) with k > 0 first")
+        B, D = self.rp_bins, self.rp_max_d
+        rec = self.rp_hist_rec.cpu().numpy().astype(np.int64)
+        pairs = None if self.rp_pair_rec is None else self.rp_pair_rec.cpu().numpy()
+        edges = self.rp_edges.cpu().numpy()
+        out = []
+        for k in range(self.R):
+            its = np.arange(self._rp_t0, self.last_iteration(k) + 1, self.rp_every, dtype=np.int64)
+            d = dict(reputation_history_iters=its,
+                     reputation_hist_history=rec[k, :len(its)].reshape(len(its), 2, B).copy(),
+                     reputation_bin_edges=edges[k].copy())
+            if pairs is not None:
+                r = pairs[k, :len(its)]
+                d.update(reputation_sum_history=r[:, 0].copy(), reputation_pair_rows_history=r[:, 1:D + 2].copy(),
+                         reputation_pair_cols_history=r[:, D + 2:].copy(),
+                         reputation_unit=np.float64(self.rep_units[k]))
+            out.append(d)
         return out
 
     def finalize_history(self):

@@ -43,6 +43,14 @@ class SPGG:
     # write them as three more datasets (CORRELATION_DATASETS); 0: the reference's file.
     correlation_history_every = 0
     correlation_max_distance = None
+    # k > 0: also record the joint histogram strategy x reputation bin of (S_t, R_t)
+    # (reputation_history_bins bins over R_min .. R_max) at t = 1, 1+k, ... on the device and, with
+    # reputation_max_distance not None, the pair sums of the int8 reputation plane at the distances
+    # 0 .. reputation_max_distance; written as more datasets (REPUTATION_DATASETS); 0: the
+    # reference's file.
+    reputation_history_every = 0
+    reputation_history_bins = 20
+    reputation_max_distance = None
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -151,13 +159,16 @@ class SPGG:
         try:
             every = int(self.cluster_history_every or 0)
             co_every = int(self.correlation_history_every or 0)
+            rp_every = int(self.reputation_history_every or 0)
             eng.run(snapshots=True, png=self.save_png, clusters_every=every,
                     clusters_periodic=bool(self.cluster_history_periodic), correlations_every=co_every,
-                    correlations_max_d=self.correlation_max_distance)
+                    correlations_max_d=self.correlation_max_distance, reputation_every=rp_every,
+                    reputation_bins=int(self.reputation_history_bins), reputation_max_d=self.reputation_max_distance)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (host above its supported side)
             cluster_hist = eng.cluster_histories()[0] if every > 0 else None
             correlation_hist = eng.correlation_histories()[0] if co_every > 0 else None
+            reputation_hist = eng.reputation_histories()[0] if rp_every > 0 else None
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -188,7 +199,8 @@ class SPGG:
         # the datasets last: the reference fills its file after the loop, so a write
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
-                       clusters=clusters, cluster_hist=cluster_hist, correlation_hist=correlation_hist)
+                       clusters=clusters, cluster_hist=cluster_hist, correlation_hist=correlation_hist,
+                       reputation_hist=reputation_hist)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -210,8 +222,14 @@ CLUSTER_DATASETS = ("cluster_history_iters", "cluster_count_history", "largest_c
 CORRELATION_DATASETS = ("correlation_history_iters", "pair_count_rows_history", "pair_count_cols_history")
 
 
+# the last four only with reputation_max_distance set (BatchEngine.reputation_histories)
+REPUTATION_DATASETS = ("reputation_history_iters", "reputation_hist_history", "reputation_bin_edges",
+                       "reputation_sum_history", "reputation_pair_rows_history", "reputation_pair_cols_history",
+                       "reputation_unit")
+
+
 def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
-                   cluster_hist=None, correlation_hist=None):
+                   cluster_hist=None, correlation_hist=None, reputation_hist=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
     the final state.  Shared by SPGG.run and the batched sweep runner.
@@ -219,7 +237,9 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
     clusters: the final cluster sizes (BatchEngine.cluster_sizes) instead of labelling S on the
     host here; cluster_hist: the in-run cluster record (BatchEngine.cluster_histories), written
     as the CLUSTER_DATASETS after the reference's own; correlation_hist: the in-run pair-count
-    record (BatchEngine.correlation_histories), written as the CORRELATION_DATASETS after those.
+    record (BatchEngine.correlation_histories), written as the CORRELATION_DATASETS after those;
+    reputation_hist: the in-run reputation record (BatchEngine.reputation_histories), written as
+    the REPUTATION_DATASETS it holds after those.
     The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
@@ -258,6 +278,12 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
         if correlation_hist is not None:
             for name in CORRELATION_DATASETS:
                 data_file.create_dataset(name, data=np.asarray(correlation_hist[name], dtype=np.int64))
+        if reputation_hist is not None:
+            for name in REPUTATION_DATASETS:
+                if name in reputation_hist:
+                    float_valued = name in ("reputation_bin_edges", "reputation_unit")
+                    data_file.create_dataset(name, data=np.asarray(
+                        reputation_hist[name], dtype=np.float64 if float_valued else np.int64))
 
 
 def track_positions(L):
