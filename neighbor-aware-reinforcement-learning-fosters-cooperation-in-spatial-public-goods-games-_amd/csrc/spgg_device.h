@@ -153,6 +153,14 @@ __device__ __forceinline__ double max_f64(double a, double b) {
   return r;
 }
 
+// max(a, 0.0) with the zero as the instruction's inline constant: through max_f64 the
+// "v" operand costs a v_mov_b64 of the constant into a register pair at every use.
+__device__ __forceinline__ double max0_f64(double a) {
+  double r;
+  asm("v_max_f64 %0, %1, 0" : "=v"(r) : "v"(a));
+  return r;
+}
+
 // Max over the wave, in every lane: permlane32/16 swaps, then DPP partners
 // l^8, l^7, l^2, l^1 (together they span the 16-lane row), no LDS.
 template <int MASK>

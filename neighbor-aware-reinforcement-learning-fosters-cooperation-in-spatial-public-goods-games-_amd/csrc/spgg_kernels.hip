@@ -564,22 +564,28 @@ __device__ __forceinline__ void build_plus_counts_prev(uint8_t* pc, const uint8_
     pc[y * kPcPitch + lane] = (uint8_t)(cnt << 3);
   }
 }
+// Both planes of a compile-time-width tile in ONE pass over the staged S window: bit 0 (s_t) and
+// bit 3 (s_{t-1}) of an S byte lie in one byte, so the five-cell sum of S & 0x09 holds the
+// defector count of S_t in bits 0-2 and that of S_{t-1}, already x8, in bits 3-5 (<= 5 + 40: no
+// byte carries into the next).  pc gets the first x8, pp (when `prev`: workgroup-uniform) the
+// second; one set of LDS reads and funnel shifts instead of two, and no defector-bit plane.
 template <int DWPR>
-__device__ __forceinline__ void build_plus_counts_prev_dw(uint8_t* pc, const uint8_t* splane, int sw, int rows,
-                                                          int soff, int tid) {
+__device__ __forceinline__ void build_plus_counts_both_dw(uint8_t* pc, uint8_t* pp, const uint8_t* splane, int sw,
+                                                          int rows, int soff, bool prev, int tid) {
   const uint32_t s0 = 8u * soff, s1 = s0 + 8u, s2 = s0 + 16u;
   const int swd = sw >> 2;
-  constexpr uint32_t kB3 = 0x01010101u;
+  constexpr uint32_t kB03 = 0x09090909u;
   for (int task = tid; task < rows * DWPR; task += kBlock) {
     const int y = task / DWPR, xd = task - (task / DWPR) * DWPR;
     const uint32_t* r0 = reinterpret_cast<const uint32_t*>(splane) + y * swd + xd;
-    const uint32_t a0 = (r0[0] >> 3) & kB3, a1 = (r0[1] >> 3) & kB3;
-    const uint32_t b0 = (r0[swd] >> 3) & kB3, b1 = (r0[swd + 1] >> 3) & kB3;
-    const uint32_t c0 = (r0[2 * swd] >> 3) & kB3, c1 = (r0[2 * swd + 1] >> 3) & kB3;
+    const uint32_t a0 = r0[0] & kB03, a1 = r0[1] & kB03;                      // row y    (the cell above)
+    const uint32_t b0 = r0[swd] & kB03, b1 = r0[swd + 1] & kB03;              // row y+1  (left, centre, right)
+    const uint32_t c0 = r0[2 * swd] & kB03, c1 = r0[2 * swd + 1] & kB03;      // row y+2  (the cell below)
     const uint32_t cnt = __builtin_amdgcn_alignbit(a1, a0, s1) + __builtin_amdgcn_alignbit(b1, b0, s0) +
                          __builtin_amdgcn_alignbit(b1, b0, s1) + __builtin_amdgcn_alignbit(b1, b0, s2) +
                          __builtin_amdgcn_alignbit(c1, c0, s1);
-    *reinterpret_cast<uint32_t*>(pc + y * kPcPitch + xd * 4) = cnt << 3;
+    *reinterpret_cast<uint32_t*>(pc + y * kPcPitch + xd * 4) = (cnt & 0x07070707u) << 3;
+    if (prev) *reinterpret_cast<uint32_t*>(pp + y * kPcPitch + xd * 4) = cnt & 0x38383838u;
   }
 }
 
@@ -876,15 +882,17 @@ __device__ __forceinline__ double prev_max_diff(const double* rew, int ca, int w
   double m = rw[0];
 #pragma unroll
   for (int k = 1; k < KN; ++k) m = max_f64(m, rw[k]);
-  return max_f64(m - r0, 0.0);  // max(0, md): one v_max_f64 (md is never -0)
+  return max0_f64(m - r0);  // max(0, md): one v_max_f64 (md is never -0)
 }
 
 // |diag_alpha * td'| of iteration t-1 (spgg.py:446-475) from the table after its TD update
 // (q, qb: before the NI term), its entry e = (s_old, a), its new state sn and reward rew --
 // what td_update returned in launch t-1.  eps_prev: eps of iteration t-1 (Expected SARSA).
+// *qe (single-table operators): the entry Q'[s, a] itself, which the caller's NI term updates.
 template <int ALG, typename PT>
 __device__ __forceinline__ float prev_diag_td(const double (&q)[4], const double (&qb)[ALG == ALG_DQ ? 4 : 1],
-                                              int e, int sn, double rew, const PT& pg, double eps_prev) {
+                                              int e, int sn, double rew, const PT& pg, double eps_prev,
+                                              double* qe) {
   if constexpr (ALG == ALG_DQ) {
     return diag_td_dq(q, qb, e, sn, rew, pg);
   } else {
@@ -892,6 +900,7 @@ __device__ __forceinline__ float prev_diag_td(const double (&q)[4], const double
     select_row<0>(q, qb, sn, &w0, &w1);        // row s' of the updated table
     select_row<0>(q, qb, e >> 1, &o0, &o1);    // row s_old: Q'[s, a] = q1
     const double q1 = (e & 1) ? o1 : o0;
+    *qe = q1;
     const double target2 = ALG == ALG_ES ? expected_q(w0, w1, eps_prev) : max_f64(w0, w1);
     return (float)fabs(pg.diag_alpha * ((rew + pg.diag_gamma * target2) - q1));
   }
@@ -1069,6 +1078,9 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // PERSIST: the stored pending record (md, atd) of the owned agents carried in registers from one
   // iteration to the next (timing variant SPGG_PERSIST_NORECOMP: through global memory instead)
   constexpr bool CARRY = PERSIST && !SPGG_PERSIST_NORECOMP;
+  // both plus-count planes from the S window in one pass (build_plus_counts_both_dw); the
+  // defector-bit plane is then neither staged nor read
+  constexpr bool BOTH = RECOMP && TWC > 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   // XCD-aware placement: blocks b, b+8, b+16... share an XCD (round-robin
@@ -1134,6 +1146,13 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // (PERSIST: q, qb, md_own, atd_own and the slots carry over from one iteration to the next)
   int rc[APT];
   unsigned vbits = 0;  // bit u: slot u holds an owned agent
+  // Slots u < NFULL hold an owned agent in every thread of every tile (width-40 tiles of the
+  // operator's most agents per thread: the host's twc_of admits them only where the smallest
+  // tile has more than (APT-1)*kBlock agents), so their ownership mask is the constant 1: the
+  // history terms' fma(x, 1.0, v) is v + x (the same single rounding) and the selects and counter
+  // masks fold away.  Only the last slot can be a shadow slot.
+  constexpr int NFULL = (TWC == 40 && APT == spgg_impl::apt_of(ALG)) ? APT - 1 : 0;
+  auto owned = [&](int u) -> uint32_t { return u < NFULL ? 1u : (vbits >> u) & 1u; };
   double q[APT][4];
   double qb[APT][QB ? 4 : 1];
   double md_own[APT];
@@ -1195,7 +1214,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
 #pragma unroll
     for (int u = 0; u < APT; ++u) {
       const int k = tid + u * kBlock;
-      const bool own = k < n_own;
+      const bool own = u < NFULL || k < n_own;
       // (TWC tiles: odd lanes shadow the tile's second agent, so lane pairs keep holding
       // agent pairs (2m, 2m+1) -- the Philox blocks of phase 1b are shared per lane pair)
       rc[u] = own ? (r << 16) | (c << 8) : (TWC ? (tid & 1) << 8 : 0);
@@ -1328,7 +1347,14 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   const double lam_rcp = uniform_f64(1.0 / lam_den);  // IEEE, once per workgroup
   const double eps_t = a.eps[(size_t)rep * a.slots + t];
   const double eps_prev = ALG == ALG_ES && pending ? a.eps[(size_t)rep * a.slots + t - 1] : 0.0;
-  const uint64_t eps53 = uniform_u64(u53_threshold(eps_t));  // rand < eps_t as an integer compare
+  // rand < eps_t as an integer compare.  Philox draws compare 31 bits against ceil(eps53 / 2^22)
+  // (philox_decide) = ceil(eps_t * 2^31) (ceil(ceil(y) / m) = ceil(y / m) for an integer m; the
+  // scaling is exact), so that bound is made directly -- three f64 ops instead of the 64-bit
+  // conversion -- and handed on as the multiple of 2^22 philox_decide takes it back from
+  const uint64_t eps53 = RNG == SPGG_RNG_PHILOX
+                             ? (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
+                                   (int)(uint32_t)__builtin_ceil(eps_t * 2147483648.0)) << 22
+                             : uniform_u64(u53_threshold(eps_t));
   // Philox key: 64-bit seed folded with the global replica id (distinct streams per replica)
   const uint32_t pkey = (uint32_t)pg.seed ^ (uint32_t)(pg.seed >> 32) * 0x85EBCA6Bu ^
                         (uint32_t)pg.stream_id * 0xC2B2AE35u;
@@ -1337,7 +1363,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   if (tid < kParamWords) reinterpret_cast<uint64_t*>(&hps)[tid] = pword;
   else if (tid < kParamWords + 12) reinterpret_cast<uint64_t*>(tab)[tid - kParamWords] = pword;
   if constexpr (TWC > 0) {
-    winS.store(sS, ly.sw, th + 2 * HS, sD, tid);
+    winS.store(sS, ly.sw, th + 2 * HS, BOTH ? nullptr : sD, tid);
     if constexpr (!AS) {
       if constexpr (RQ) winRd.store(reinterpret_cast<uint8_t*>(sR), ly.aw, ah, nullptr, tid);
       else winR.template store<(TWC + 2 * HS + 6) / 4 * 4>(sR, ah, nullptr, tid);
@@ -1384,17 +1410,20 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     }
     return;
   }
-  // plus counts for the payoffs of phases 1b / 1c (their barrier: after phase 1a)
-  if (!fin_only) {
+  // plus counts for the payoffs of phases 1b / 1c (their barrier: after phase 1a) and, for the
+  // recomputed NI record, of iteration t-1 (BOTH: one pass builds the two planes)
+  const bool rec_prev = RECOMP && pending && kappa != 0.0;  // workgroup-uniform
+  if constexpr (BOTH) {
+    if (!fin_only || rec_prev)
+      build_plus_counts_both_dw<(TWC + 2 * HA + 2 + 3) / 4>(sPC, sPP, sS, ly.sw, ah + 2, soffS, rec_prev, tid);
+  } else if (!fin_only) {
     if constexpr (TWC > 0) build_plus_counts_dw<(TWC + 2 * HA + 2 + 3) / 4>(sPC, sD, ly.sw, ah + 2, soffS, tid);
     else build_plus_counts(sPC, sDv, ly.sw, ah + 2, tid);
   }
   // the rewards of iteration t-1 over the region (tile + ring), into sRew (phase 1a reads them;
   // phases 1b / 1c overwrite them with iteration t's after the barrier that ends phase 1a)
-  const bool rec_prev = RECOMP && pending && kappa != 0.0;  // workgroup-uniform
   if (rec_prev) {
-    if constexpr (TWC > 0) build_plus_counts_prev_dw<(TWC + 2 * HA + 2 + 3) / 4>(sPP, sS, ly.sw, ah + 2, soffS, tid);
-    else build_plus_counts_prev(sPP, sSv, ly.sw, ah + 2, tid);
+    if constexpr (!BOTH) build_plus_counts_prev(sPP, sSv, ly.sw, ah + 2, tid);
     __syncthreads();  // both plus-count planes
     const int dr = kBlock / aw, dc = kBlock - (kBlock / aw) * aw;
     int ry = tid / aw, rx = tid - (tid / aw) * aw;
@@ -1461,31 +1490,43 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     if (pending) {
 #pragma unroll
       for (int u = 0; u < APT; ++u) {
-        const double vmu = (vbits >> u) & 1 ? 1.0 : 0.0;
+        const double vmu = owned(u) ? 1.0 : 0.0;
         const uint8_t b = sb[u];
         const int e = pending_entry(b);
         // kappa == 0 (a replica-uniform skip): nu = +0, q + 0 == q (Q never holds -0.0:
         // U(-0.01,0.01) draws and TD sums of finite values give +0 for exact zeros),
         // and the NI percent is exactly 0
         if (kappa != 0.0) {
-          double mdp;
+          double mdp, qe = 0.0;
           float atdv;
           if constexpr (RECOMP) {  // the record of t-1 from its rewards and the held table
             const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
             const int ca = (r + HA) * ly.aw + (c + HA);
             mdp = prev_max_diff<M2>(sRew, ca, ly.aw);
-            atdv = prev_diag_td<ALG>(q[u], qb[u], e, (b >> 4) & 1, sRew[ca], hp, eps_prev);
+            atdv = prev_diag_td<ALG>(q[u], qb[u], e, (b >> 4) & 1, sRew[ca], hp, eps_prev, &qe);
           } else {
             mdp = md_own[u];
             atdv = atd_own[u];
           }
           const double nu = pending_nu(b, mdp, kappa, lam_den, lam_rcp);
-          // Q[s,a] += nu as exact masked FMAs: fma(1, nu, x) = x + nu, fma(0, nu, x) = x
+          if constexpr (RECOMP && !QB) {
+            // Q[s,a] += nu on the entry prev_diag_td selected, written back with the lane masks of
+            // s and a combined on the scalar unit (as td_update's): one add and eight selects
+            // instead of four compares, four mask selects and four FMAs
+            const double x = qe + nu;
+            const bool s1 = (e & 2) != 0, a1 = (e & 1) != 0;
+            q[u][0] = (!s1 && !a1) ? x : q[u][0];
+            q[u][1] = (!s1 && a1) ? x : q[u][1];
+            q[u][2] = (s1 && !a1) ? x : q[u][2];
+            q[u][3] = (s1 && a1) ? x : q[u][3];
+          } else {
+            // Q[s,a] += nu as exact masked FMAs: fma(1, nu, x) = x + nu, fma(0, nu, x) = x
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const double m = e == k ? 1.0 : 0.0;
-            q[u][k] = __builtin_fma(m, nu, q[u][k]);
-            if constexpr (QB) qb[u][k] = __builtin_fma(m, nu, qb[u][QB ? k : 0]);  // both tables (spgg.py:496-502)
+            for (int k = 0; k < 4; ++k) {
+              const double m = e == k ? 1.0 : 0.0;
+              q[u][k] = __builtin_fma(m, nu, q[u][k]);
+              if constexpr (QB) qb[u][k] = __builtin_fma(m, nu, qb[u][QB ? k : 0]);  // both tables (spgg.py:496-502)
+            }
           }
           ni_rows |= (1u << (e >> 1)) << (2 * u);
           // NI percent (spgg.py:512; x100 applied to the workgroup total), in f32:
@@ -1547,7 +1588,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     for (int u = 0; u < APT; ++u) {
       if (fin_only) continue;
       const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
-      const uint32_t one = (vbits >> u) & 1;
+      const uint32_t one = owned(u);
       const double vmu = one ? 1.0 : 0.0;
       const int cs = (r + HS) * ly.sw + (c + HS);
       const int ca = (r + HA) * ly.aw + (c + HA);
@@ -1669,7 +1710,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     for (int u = 0; u < APT; ++u) {
       const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
       const int ca = (r + HA) * ly.aw + (c + HA);
-      const uint32_t one = (vbits >> u) & 1;
+      const uint32_t one = owned(u);
       const int act = rc[u] & 1, so = (rc[u] >> 1) & 1;
       const double rew = sRew[ca];
       int sn;                                               // spgg.py:423
@@ -1727,8 +1768,8 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
         if constexpr (M2) ks = better ? kk : ks;
       }
       const int dp = abest == act ? 1 : 0;
-      const double mdp = max_f64(md, 0.0);  // max(0, md), one op (md is never -0: rewards are never -0)
-      bmax = max_f64(bmax, mdp);
+      const double mdp = max0_f64(md);  // max(0, md), one op (md is never -0: rewards are never -0)
+      bmax = u == 0 ? mdp : max_f64(bmax, mdp);  // (mdp >= +0: the first slot's max with 0 is mdp itself)
       // max(0, max_diff) feeds only the next launch's NI term, which is +0 when kappa == 0
       // (phase 1a and the ring skip it): not stored then (-8 B/agent-step for those replicas)
       if constexpr (CARRY) md_own[u] = mdp;
@@ -2695,9 +2736,15 @@ namespace {
 
 // Compile-time tile width of the step kernel (0: run-time width): every tile
 // full width, L >= 2 * window width (L % 4 == 0 for the aligned-dword window
-// staging), window rows within the staging register budget (TH <= 25).
+// staging), window rows within the staging register budget (TH <= 25).  Width 40: every tile,
+// the last (shorter) row of tiles included, fills all but the last agent slot of each thread
+// (step_impl's NFULL: those slots carry no ownership mask); the chooser's 40-wide tiles divide L
+// (40 x 24, 40 x 25), so only a tuning tile shape can fail this and takes the run-time-width kernel.
 int twc_of(const spgg_config& cfg, int TW, int TH) {
-  if (TW == 40 && cfg.L % 40 == 0 && cfg.L >= 120 && TH <= 25) return 40;
+  const int th_min = cfg.L % TH ? cfg.L % TH : TH;
+  if (TW == 40 && cfg.L % 40 == 0 && cfg.L >= 120 && TH <= 25 &&
+      th_min * 40 > (spgg_impl::apt_of(cfg.algorithm) - 1) * kBlock)
+    return 40;
   // two agents per thread (spgg_create): 20 x 25 tiles, kernels of compile-time width 20
   if (TW == 20 && cfg.L % 20 == 0 && cfg.L >= 60 && TH <= 25 && cfg.algorithm != SPGG_ALG_DOUBLE_Q) return 20;
   return 0;

@@ -1,0 +1,173 @@
+"""Static issue ledger of one step-kernel instance: VALU count and weighted issue cycles per
+barrier segment and per source function.
+
+    python tools/issue_ledger.py [--tu 0] [--instance false,false,true,2,4,40,0] [--top 25]
+                                 [--asm file.s] [--keep file.s]
+
+Rebuilds one translation unit of csrc/spgg_kernels.hip to gfx950 assembly with the build's own
+compiler and flags (spgg_amd.build: HIPCC, FLAGS, -DSPGG_TU=<tu>) plus -gline-tables-only (line
+directives only: the code is the build's), or reads --asm.  The instance is
+spgg_step_kernel<M2, AS, RQ, RNG, APT, TWC, ALG>; the default is the one bench.py's cfg3 runs.
+
+Weights (MI355X: a wave64 op issues over a 32-lane SIMD datapath): 2 cycles for a 32-bit VALU
+op, 4 for f64 / 64-bit ops, 8 for the quarter-rate 32-bit multiplies and v_mad_u64_u32 and for
+v_rcp_f64.  Counts are static: a loop body counts once, whatever its trip count.
+Instructions are counted by class (the v_ / s_ / ds_ / global_ prefixes) alone.
+
+A line belongs to the function whose definition encloses it in its source file (the innermost
+inlined callee the line tables name), and to the segment between the s_barriers around it.
+"""
+import argparse
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HEAVY = {"v_mad_u64_u32": 8, "v_mul_lo_u32": 8, "v_mul_hi_u32": 8, "v_rcp_f64": 8,
+         "v_rcp_f32_e32": 4}
+WIDE = ("f64", "b64", "u64", "i64")
+
+
+def weight(op):
+    return HEAVY.get(op, 4 if any(w in op for w in WIDE) else 2)
+
+
+def mangled(instance):
+    out = "spgg_step_kernelI"
+    for f in instance.split(","):
+        f = f.strip()
+        out += {"false": "Lb0E", "true": "Lb1E"}.get(f) or f"Li{int(f)}E"
+    return out + "E"
+
+
+def assemble(tu, keep):
+    import spgg_amd.build as B
+    out = keep or os.path.join(tempfile.mkdtemp(prefix="ledger"), f"tu{tu}.s")
+    cmd = [B.HIPCC, *B.FLAGS, '-DSPGG_BUILD_ID="ledger"', f"-DSPGG_TU={tu}", f"-I{B.INC}", "-gline-tables-only",
+           "--cuda-device-only", "-S", B.SRC[0], "-o", out]
+    subprocess.run(cmd, check=True)
+    return out
+
+
+_FN = re.compile(r"^\s{0,2}(?:template\s*<[^>]*>\s*)?(?:static\s+|inline\s+|constexpr\s+|__host__\s+|__device__\s+|"
+                 r"__global__\s+|__forceinline__\s+|__launch_bounds__\([^)]*\)\s+|\([^)]*\)\s*)*"
+                 r"[\w:<>,\s\*&]*?\b(\w+)\s*\([^;]*$")
+
+
+def function_map(path):
+    """line -> name of the enclosing function definition (brace depth <= 1: namespace or struct level)."""
+    try:
+        src = open(path, errors="replace").read().split("\n")
+    except OSError:
+        return {}
+    owner, cur, depth, fdepth, pending = {}, None, 0, None, None
+    for i, l in enumerate(src, 1):
+        code = l.split("//")[0]
+        if cur is None and ("__device__" in code or "__global__" in code) and "(" in code:
+            m = _FN.match(code)
+            if m and m.group(1) not in ("if", "for", "while", "switch", "return", "sizeof"):
+                pending = m.group(1)
+        if pending and cur is None and "{" in code:
+            cur, fdepth, pending = pending, depth, None
+        elif pending and ";" in code and "{" not in code:
+            pending = None
+        if cur:
+            owner[i] = cur
+        depth += code.count("{") - code.count("}")
+        if cur and depth <= fdepth:
+            cur = None
+    return owner
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tu", type=int, default=0)
+    ap.add_argument("--instance", default="false,false,true,2,4,40,0")
+    ap.add_argument("--top", type=int, default=25, help="source lines listed")
+    ap.add_argument("--asm", default=None)
+    ap.add_argument("--keep", default=None)
+    a = ap.parse_args()
+    path = a.asm or assemble(a.tu, a.keep)
+    s = open(path).read().split("\n")
+    key = mangled(a.instance)
+    try:
+        st = next(i for i, l in enumerate(s) if key in l and re.match(r"^[\w$.]+:", l))
+    except StopIteration:
+        sys.exit(f"no kernel symbol containing {key} in {path}")
+    files = {}
+    for l in s:
+        if l.startswith("\t.file"):
+            m = re.match(r'\t\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
+            if m:
+                d, f = (m.group(2), m.group(3)) if m.group(3) else ("", m.group(2))
+                files[m.group(1)] = f if os.path.isabs(f) else os.path.join(d, f)
+    fmaps = {}
+    seg = [collections.Counter()]
+    fn = collections.defaultdict(collections.Counter)
+    ln = collections.defaultdict(collections.Counter)
+    cur = (None, 0)
+    for l in s[st + 1:]:
+        if l.startswith(".Lfunc_end"):
+            break
+        if l.startswith("\t.loc"):
+            p = l.split()
+            cur = (files.get(p[1], p[1]), int(p[2]))
+            continue
+        t = l.strip()
+        if not l.startswith("\t") or not t or t.startswith((".", ";")):
+            continue
+        op = t.split()[0]
+        c = seg[-1]
+        if op == "s_barrier":
+            c["salu"] += 1
+            seg.append(collections.Counter())
+        elif op.startswith("v_"):
+            f = cur[0]
+            if f not in fmaps:
+                fmaps[f] = function_map(f) if f else {}
+            name = fmaps[f].get(cur[1], "?")
+            w = weight(op)
+            for k in (c, fn[name], ln[(os.path.basename(f or "?"), cur[1], name)]):
+                k["valu"] += 1
+                k["cyc"] += w
+            fn[name][f"seg{len(seg) - 1}"] += w
+        elif op.startswith("s_"):
+            c["salu"] += 1
+        elif op.startswith("ds_"):
+            c["lds"] += 1
+        elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+            c["vmem"] += 1
+    meta = {}
+    for l in s[st:]:
+        m = re.match(r"\s*[;.]\s*(?:\.?)(NumVgprs|ScratchSize|Occupancy|NumSgprs|LDSByteSize)\s*:\s*(\d+)", l)
+        if m and m.group(1) not in meta:
+            meta[m.group(1)] = int(m.group(2))
+        if len(meta) == 5 or l.startswith("\t.end_amdhsa_kernel"):
+            if len(meta) >= 3:
+                break
+    tot = sum(c["cyc"] for c in seg)
+    nv = sum(c["valu"] for c in seg)
+    print(f"instance spgg_step_kernel<{a.instance}>  (TU {a.tu})")
+    print(f"static VALU {nv}  weighted VALU cycles {tot}  SALU {sum(c['salu'] for c in seg)}  "
+          f"LDS {sum(c['lds'] for c in seg)}  VMEM {sum(c['vmem'] for c in seg)}  " +
+          "  ".join(f"{k} {v}" for k, v in sorted(meta.items())))
+    print("\nper barrier segment")
+    for i, c in enumerate(seg):
+        print(f"  seg {i:2d}: valu {c['valu']:5d}  cyc {c['cyc']:5d} ({100 * c['cyc'] / max(tot, 1):4.1f}%)  "
+              f"salu {c['salu']:4d}  lds {c['lds']:4d}  vmem {c['vmem']:3d}")
+    print("\nper source function (weighted cycles by segment)")
+    for name, c in sorted(fn.items(), key=lambda kv: -kv[1]["cyc"]):
+        segs = " ".join(f"s{i}:{c[f'seg{i}']}" for i in range(len(seg)) if c[f"seg{i}"])
+        print(f"  {name:28s} valu {c['valu']:5d}  cyc {c['cyc']:5d} ({100 * c['cyc'] / max(tot, 1):4.1f}%)  {segs}")
+    print(f"\ntop {a.top} source lines")
+    for (f, line, name), c in sorted(ln.items(), key=lambda kv: -kv[1]["cyc"])[:a.top]:
+        print(f"  {c['cyc']:5d} {100 * c['cyc'] / max(tot, 1):4.1f}%  n={c['valu']:4d}  {f}:{line}  ({name})")
+
+
+if __name__ == "__main__":
+    main()
