@@ -2768,6 +2768,35 @@ int hip_check(spgg_ctx* c, hipError_t e, const char* what) {
   return fail(c, SPGG_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// The shared prechecks of the observable entry points (spgg_payoff, spgg_clusters, spgg_correlations,
+// spgg_reputation_*): arguments present, the context bound (with its parameters if the kernel reads
+// them), t >= 1.
+int observable_check(spgg_ctx* c, const char* fn, bool args, bool params, int32_t t) {
+  if (!c || !args) return fail(c, SPGG_E_ARG, "null argument");
+  if (!c->bound || (params && !c->params_set))
+    return fail(c, SPGG_E_STATE, std::string(fn) + (params ? " before bind/set_params" : " before bind"));
+  if (t < 1) return fail(c, SPGG_E_ARG, std::string(fn) + ": bad t");
+  return SPGG_OK;
+}
+
+// Their range checks: the lattice side against the kernel's limit (`why` names what sets it) and,
+// for those that take one, max_d within 0 .. L / 2.
+int range_check(spgg_ctx* c, const char* fn, int max_side, const char* why, int32_t max_d = 0) {
+  if (c->cfg.L > max_side)
+    return fail(c, SPGG_E_ARG, std::string(fn) + ": L = " + std::to_string(c->cfg.L) + " exceeds the supported side " +
+                                   std::to_string(max_side) + " (" + why + ")");
+  if (max_d < 0 || max_d > c->cfg.L / 2)
+    return fail(c, SPGG_E_ARG, std::string(fn) + ": max_d = " + std::to_string(max_d) + " outside 0 .. L / 2 = " +
+                                   std::to_string(c->cfg.L / 2));
+  return SPGG_OK;
+}
+
+int max_side_out(const spgg_ctx* c, int32_t* side, int value) {
+  if (!c || !side) return SPGG_E_ARG;
+  *side = value;
+  return SPGG_OK;
+}
+
 // A tuning knob's value (spgg_abi.h, "Environment knobs"), read only when SPGG_TUNING=1: a stray
 // variable in a user's environment never changes the layout or the schedule of a production run.
 const char* tuning_env(const char* name) {
@@ -3624,9 +3653,7 @@ int spgg_draw_range(spgg_ctx* c, int32_t t0, int32_t t1, void* stream) {
 }
 
 int spgg_payoff(spgg_ctx* c, int32_t t, double* out, void* stream) {
-  if (!c || !out) return fail(c, SPGG_E_ARG, "null argument");
-  if (!c->bound || !c->params_set) return fail(c, SPGG_E_STATE, "spgg_payoff before bind/set_params");
-  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_payoff: bad t");
+  if (const int rc = observable_check(c, "spgg_payoff", out, true, t)) return rc;
   const dim3 grid((c->n + kBlock - 1) / kBlock, c->cfg.n_rep);
   hipLaunchKernelGGL(spgg_payoff_kernel, grid, dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
                      c->buf.S[(t - 1) & 1], c->d_params, out, c->cfg.L, c->n);
@@ -3634,56 +3661,38 @@ int spgg_payoff(spgg_ctx* c, int32_t t, double* out, void* stream) {
 }
 
 int spgg_clusters_max_side(const spgg_ctx* c, int32_t* side) {
-  if (!c || !side) return SPGG_E_ARG;
-  *side = spgg_cl::kMaxSide;
-  return SPGG_OK;
+  return max_side_out(c, side, spgg_cl::kMaxSide);
 }
 
 int spgg_clusters(spgg_ctx* c, int32_t t, int32_t periodic, int32_t* sizes, int32_t* rec, int64_t rec_stride,
                   void* stream) {
-  if (!c || !rec) return fail(c, SPGG_E_ARG, "null argument");
-  if (!c->bound) return fail(c, SPGG_E_STATE, "spgg_clusters before bind");
-  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_clusters: bad t");
-  if (c->cfg.L > spgg_cl::kMaxSide)
-    return fail(c, SPGG_E_ARG, "spgg_clusters: L = " + std::to_string(c->cfg.L) + " exceeds the supported side " +
-                                   std::to_string(spgg_cl::kMaxSide) + " (the lattice is labelled in LDS)");
+  if (const int rc = observable_check(c, "spgg_clusters", rec, false, t)) return rc;
+  if (const int rc = range_check(c, "spgg_clusters", spgg_cl::kMaxSide, "the lattice is labelled in LDS")) return rc;
   spgg_cl::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, periodic, sizes, rec,
                         rec_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_clusters launch");
 }
 
 int spgg_correlations_max_side(const spgg_ctx* c, int32_t* side) {
-  if (!c || !side) return SPGG_E_ARG;
-  *side = spgg_co::kMaxSide;
-  return SPGG_OK;
+  return max_side_out(c, side, spgg_co::kMaxSide);
 }
 
 int spgg_correlations(spgg_ctx* c, int32_t t, int32_t max_d, int32_t* out, int64_t out_stride, void* stream) {
-  if (!c || !out) return fail(c, SPGG_E_ARG, "null argument");
-  if (!c->bound) return fail(c, SPGG_E_STATE, "spgg_correlations before bind");
-  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_correlations: bad t");
-  if (c->cfg.L > spgg_co::kMaxSide)
-    return fail(c, SPGG_E_ARG, "spgg_correlations: L = " + std::to_string(c->cfg.L) + " exceeds the supported side " +
-                                   std::to_string(spgg_co::kMaxSide) + " (the lattice is packed into LDS)");
-  if (max_d < 0 || max_d > c->cfg.L / 2)
-    return fail(c, SPGG_E_ARG, "spgg_correlations: max_d = " + std::to_string(max_d) + " outside 0 .. L / 2 = " +
-                                   std::to_string(c->cfg.L / 2));
+  if (const int rc = observable_check(c, "spgg_correlations", out, false, t)) return rc;
+  if (const int rc = range_check(c, "spgg_correlations", spgg_co::kMaxSide, "the lattice is packed into LDS", max_d))
+    return rc;
   spgg_co::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, max_d, out, out_stride,
                   reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_correlations launch");
 }
 
 int spgg_reputation_max_side(const spgg_ctx* c, int32_t* side) {
-  if (!c || !side) return SPGG_E_ARG;
-  *side = spgg_rp::kMaxSide;
-  return SPGG_OK;
+  return max_side_out(c, side, spgg_rp::kMaxSide);
 }
 
 int spgg_reputation_hist(spgg_ctx* c, int32_t t, int32_t bins, const double* edges, int32_t* out, int64_t out_stride,
                          void* stream) {
-  if (!c || !edges || !out) return fail(c, SPGG_E_ARG, "null argument");
-  if (!c->bound || !c->params_set) return fail(c, SPGG_E_STATE, "spgg_reputation_hist before bind/set_params");
-  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_reputation_hist: bad t");
+  if (const int rc = observable_check(c, "spgg_reputation_hist", edges && out, true, t)) return rc;
   if (bins < 1 || bins > spgg_rp::kMaxBins)
     return fail(c, SPGG_E_ARG, "spgg_reputation_hist: bins = " + std::to_string(bins) + " outside 1 .. " +
                                    std::to_string(spgg_rp::kMaxBins));
@@ -3696,18 +3705,11 @@ int spgg_reputation_hist(spgg_ctx* c, int32_t t, int32_t bins, const double* edg
 }
 
 int spgg_reputation_pairs(spgg_ctx* c, int32_t t, int32_t max_d, int64_t* out, int64_t out_stride, void* stream) {
-  if (!c || !out) return fail(c, SPGG_E_ARG, "null argument");
-  if (!c->bound) return fail(c, SPGG_E_STATE, "spgg_reputation_pairs before bind");
-  if (t < 1) return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: bad t");
+  if (const int rc = observable_check(c, "spgg_reputation_pairs", out, false, t)) return rc;
   if (!c->cfg.rep_int8)
     return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: the reputation buffers hold f64 (rep_int8 = 0); the pair sums "
                                "are exact integers of the int8 path only");
-  if (c->cfg.L > spgg_rp::kMaxSide)
-    return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: L = " + std::to_string(c->cfg.L) + " exceeds the supported side " +
-                                   std::to_string(spgg_rp::kMaxSide) + " (int32 lane partials)");
-  if (max_d < 0 || max_d > c->cfg.L / 2)
-    return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: max_d = " + std::to_string(max_d) + " outside 0 .. L / 2 = " +
-                                   std::to_string(c->cfg.L / 2));
+  if (const int rc = range_check(c, "spgg_reputation_pairs", spgg_rp::kMaxSide, "int32 lane partials", max_d)) return rc;
   if (out_stride < 2 * (int64_t)(max_d + 1) + 1)
     return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: out_stride below 2 * (max_d + 1) + 1");
   spgg_rp::launch_pairs(static_cast<const int8_t*>(c->buf.R[0]), static_cast<const int8_t*>(c->buf.R[1]),

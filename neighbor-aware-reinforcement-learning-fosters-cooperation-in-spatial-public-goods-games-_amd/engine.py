@@ -32,6 +32,9 @@ import torch
 
 from . import _lib as C
 from .algorithms import canonical_name
+from .records import (KINDS, next_boundary,  # noqa: F401  (the host models stay importable from here)
+                      host_cluster_sizes, host_pair_counts, correlation_function, correlation_length,
+                      reputation_bin_edges, host_reputation_pair_sums, reputation_correlation_function)
 
 SNAPSHOT_ITERS = (1, 10, 100, 1000, 5000, 10000, 20000, 30000, 40000)  # spgg.py:153
 
@@ -215,114 +218,6 @@ def plan_groups(R: int, L: int, bytes_per_replica: int, cache_bytes: int, stream
     return waves, groups, resident
 
 
-def host_cluster_sizes(S, periodic: bool = False) -> np.ndarray:
-    """int64 sizes of the 4-connected cooperator (S == 0) clusters of one lattice in label order
-    (ascending smallest raster index), on the host: scipy.ndimage.label (spgg.py:631-633);
-    periodic merges its labels across the two seams.  The path of lattices above the device
-    labelling's supported side (spgg_clusters_max_side)."""
-    from scipy.ndimage import label
-    lab, k = label(np.asarray(S) == 0)
-    counts = np.bincount(lab.ravel(), minlength=k + 1).astype(np.int64)
-    if not periodic or k == 0:
-        return counts[1:]
-    root = np.arange(k + 1)
-
-    def find(a):
-        while root[a] != a:
-            root[a] = root[root[a]]
-            a = root[a]
-        return a
-
-    for a, b in list(zip(lab[0], lab[-1])) + list(zip(lab[:, 0], lab[:, -1])):
-        if a and b:
-            ra, rb = find(a), find(b)
-            if ra != rb:
-                root[max(ra, rb)] = min(ra, rb)   # the label met first in raster order stays
-    owner = np.array([find(a) for a in range(k + 1)])
-    merged = np.bincount(owner, weights=counts, minlength=k + 1).astype(np.int64)
-    return merged[(owner == np.arange(k + 1)) & (np.arange(k + 1) > 0)]
-
-
-def host_pair_counts(S, max_d=None) -> np.ndarray:
-    """int64 (2, D+1) cooperator pair counts of one lattice on the host, D = max_d (None: L // 2):
-    with c = 1 where bit 0 of S is 0, [0, d] = sum(c & roll(c, -d, axis=1)) (pairs d apart along
-    a row) and [1, d] = sum(c & roll(c, -d, axis=0)) (along a column), periodic.  What
-    spgg_correlations counts on the device, and the path of lattices above its supported side
-    (spgg_correlations_max_side)."""
-    c = (np.asarray(S).astype(np.int64) & 1) == 0
-    L = c.shape[0]
-    D = L // 2 if max_d is None else int(max_d)
-    if c.shape != (L, L) or D < 0 or D > L // 2:
-        raise ValueError(f"host_pair_counts: a square lattice and 0 <= max_d <= L // 2, got {c.shape}, {max_d}")
-    out = np.empty((2, D + 1), dtype=np.int64)
-    for d in range(D + 1):
-        out[0, d] = np.count_nonzero(c & np.roll(c, -d, axis=1))
-        out[1, d] = np.count_nonzero(c & np.roll(c, -d, axis=0))
-    return out
-
-
-def correlation_function(rows, cols, n):
-    """Connected two-point function of the cooperator field from pair counts (any leading axes,
-    the distance last): G(d) = (rows + cols) / (2 n) - (rows[..., 0] / n)^2, n = L * L cells --
-    the direction-averaged <c(x) c(x + d)> minus the squared cooperation rate."""
-    rows, cols = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
-    rho = rows[..., :1] / n
-    return (rows + cols) / (2.0 * n) - rho * rho
-
-
-def correlation_length(G) -> float:
-    """Distance at which g = G / G[0] first falls to 1/e: the first d >= 1 with g(d) <= 1/e,
-    linearly interpolated between d - 1 and d.  nan if G[0] == 0 (an absorbed lattice), inf if g
-    never falls that far within the given distances."""
-    G = np.asarray(G, dtype=np.float64)
-    if G.ndim != 1 or G.size == 0:
-        raise ValueError("correlation_length: a one-dimensional G(d), d = 0 ..")
-    if G[0] == 0:
-        return float("nan")
-    g = G / G[0]
-    below = np.nonzero(g[1:] <= 1.0 / np.e)[0]
-    if below.size == 0:
-        return float("inf")
-    d = int(below[0]) + 1
-    return float(d - 1 + (g[d - 1] - 1.0 / np.e) / (g[d - 1] - g[d]))
-
-
-def reputation_bin_edges(R_min, R_max, bins: int = 20) -> np.ndarray:
-    """The bins + 1 edges np.histogram(x, bins=bins, range=(R_min, R_max)) uses -- with bins = 20
-    the reference's rep_bins_* datasets (spgg.py:399)."""
-    return np.histogram_bin_edges(np.empty(0), int(bins), (float(R_min), float(R_max)))
-
-
-def host_reputation_pair_sums(K, max_d=None):
-    """(sum, rows, cols) of one reputation lattice on the host, D = max_d (None: L // 2): sum =
-    K.sum(), rows[d] = sum(K * roll(K, -d, axis=1)), cols[d] = sum(K * roll(K, -d, axis=0)) for
-    d = 0 .. D, periodic.  Integer input (the int8 plane, in units of rep_unit) is summed in int64
-    and is what spgg_reputation_pairs gives on the device, exactly; float input (R itself, the f64
-    reputation path) gives the same sums in float64, rounded and so not exact.  The path of
-    f64-reputation engines and of lattices above spgg_reputation_max_side."""
-    K = np.asarray(K)
-    L = K.shape[0]
-    D = L // 2 if max_d is None else int(max_d)
-    if K.shape != (L, L) or D < 0 or D > L // 2:
-        raise ValueError(f"host_reputation_pair_sums: a square lattice and 0 <= max_d <= L // 2, got {K.shape}, {max_d}")
-    K = K.astype(np.int64 if np.issubdtype(K.dtype, np.integer) else np.float64)
-    rows, cols = np.empty(D + 1, dtype=K.dtype), np.empty(D + 1, dtype=K.dtype)
-    for d in range(D + 1):
-        rows[d] = np.sum(K * np.roll(K, -d, axis=1))
-        cols[d] = np.sum(K * np.roll(K, -d, axis=0))
-    return K.sum(), rows, cols
-
-
-def reputation_correlation_function(sum, rows, cols, n, unit):
-    """Connected two-point function of the reputation field from pair sums (any leading axes, the
-    distance last; sum without the distance axis): unit^2 * ((rows + cols) / (2 n) - (sum / n)^2),
-    n = L * L cells, unit the replica's rep_unit (1 for sums of R itself) -- the direction-averaged
-    <R(x) R(x + d)> minus the squared mean.  correlation_length applies to it as it stands."""
-    rows, cols = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
-    mean = np.asarray(sum, dtype=np.float64)[..., None] / n
-    return float(unit) ** 2 * ((rows + cols) / (2.0 * n) - mean * mean)
-
-
 # Library-made streams (spgg_stream_create) are pooled per library and device and outlive their
 # engine: torch's pinned-memory allocator keeps the events of a pinned buffer's copies (run()'s
 # stop flags) and queries them when it allocates again, so a stream destroyed under such an event
@@ -433,13 +328,8 @@ class BatchEngine:
         self.snapshots = [dict() for _ in range(self.R)]
         self.png_frames = [dict() for _ in range(self.R)]
         self._flushed = False
-        self._cl_cache = {}        # periodic -> per-replica final cluster sizes (until the next step)
-        self.cl_every, self.cl_periodic, self.cl_rec = 0, False, None   # in-run record (run)
-        self._co_cache = {}        # max_d -> (R, 2, max_d + 1) final pair counts (until the next step)
-        self.co_every, self.co_max_d, self.co_rec = 0, 0, None   # in-run pair-count record (run)
-        self._rp_cache = {}        # final reputation histograms / pair sums (until the next step)
-        self.rp_every, self.rp_bins, self.rp_max_d = 0, 0, None   # in-run reputation record (run)
-        self.rp_hist_rec = self.rp_pair_rec = self.rp_edges = None
+        self.records = {}          # name (records.KINDS) -> the in-run Record of the last run that asked for it
+        self._final_cache = {}     # final-state observables (cluster_sizes, pair_counts, ...) until the next step
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -587,14 +477,10 @@ class BatchEngine:
         C.check(self.lib.spgg_persistent(self.ctx, ctypes.byref(on), ctypes.byref(cap)), self.ctx, "spgg_persistent")
         self.persistent, self.persist_capacity = bool(on.value), int(cap.value)
         side = ctypes.c_int32()
-        C.check(self.lib.spgg_clusters_max_side(self.ctx, ctypes.byref(side)), self.ctx, "spgg_clusters_max_side")
-        self.clusters_max_side = int(side.value)   # device labelling up to this lattice side
-        C.check(self.lib.spgg_correlations_max_side(self.ctx, ctypes.byref(side)), self.ctx,
-                "spgg_correlations_max_side")
-        self.correlations_max_side = int(side.value)   # device pair counts up to this lattice side
-        C.check(self.lib.spgg_reputation_max_side(self.ctx, ctypes.byref(side)), self.ctx,
-                "spgg_reputation_max_side")
-        self.reputation_max_side = int(side.value)   # device reputation pair sums up to this lattice side
+        for kind in KINDS:   # clusters_max_side, ...: the device path of the kind up to this lattice side
+            fn = getattr(self.lib, f"spgg_{kind}_max_side")
+            C.check(fn(self.ctx, ctypes.byref(side)), self.ctx, fn.__name__)
+            setattr(self, f"{kind}_max_side", int(side.value))
 
     def _draw_layout(self, ctx):
         """(ring slots, u32 words per replica and slot, key-snapshot slots) of the draw records."""
@@ -724,9 +610,7 @@ class BatchEngine:
         n_steps = min(n_steps, self.T - self.t + 1)
         if n_steps <= 0:
             return 0
-        self._cl_cache = {}
-        self._co_cache = {}
-        self._rp_cache = {}
+        self._final_cache = {}
         if self.rng == "inject":
             for _ in range(n_steps):
                 self._inject(self.t)
@@ -825,75 +709,25 @@ class BatchEngine:
         replicas' launches change nothing, so results are unaffected; only the wall time of a
         run that absorbs early carries that turn.  Snapshot iterations sync.
 
-        clusters_every = k > 0: the cluster record of S_t (spgg_clusters: number of cooperator
-        clusters, largest cluster, C-D bonds; clusters_periodic: wrapped lattice) is taken at
-        t = 1, 1+k, 1+2k, ... on each replica group's own stream between the step launches of
-        t-1 and t (a turn boundary there, no host sync; the stop-flag copies stay `chunk`
-        iterations apart); read it with cluster_histories().  With 0 nothing else is enqueued
-        than before.
-
-        correlations_every = k > 0: the cooperator pair counts of S_t (spgg_correlations) at the
-        distances 0 .. correlations_max_d (None: L // 2) are recorded at t = t0, t0+k, ... (t0
-        the iteration the run starts at) in the same way, and together with the cluster record
-        if both are set; read them with correlation_histories().  The record holds one row per
-        recorded iteration.  With 0 nothing else is enqueued than before.
-
-        reputation_every = k > 0: the joint histogram strategy x reputation bin of (S_t, R_t)
-        (spgg_reputation_hist; reputation_bins bins over each replica's R_min .. R_max, the
-        reference's edges) is recorded at t = t0, t0+k, ... in the same way, beside the other two
-        records; with reputation_max_d not None also the pair sums of the int8 reputation plane
-        (spgg_reputation_pairs) at the distances 0 .. reputation_max_d -- a ValueError on an
-        f64-reputation engine or above reputation_max_side, before anything is enqueued.  Read
-        them with reputation_histories().  With 0 nothing else is enqueued than before."""
-        rp_every = int(reputation_every)
-        if rp_every < 0:
-            raise ValueError("reputation_every must be >= 0")
-        rp_bins = int(reputation_bins)
-        rp_d = None if reputation_max_d is None else int(reputation_max_d)
-        if rp_every and not 1 <= rp_bins <= 256:
-            raise ValueError(f"reputation_bins must lie in 1 .. 256, got {rp_bins}")
-        if rp_every and rp_d is not None:
-            if not self.rep_int8:
-                raise ValueError("reputation_max_d: the pair sums are exact integers of the int8 reputation path; "
-                                 "this engine holds f64 reputation (non-dyadic gains or bounds) -- sum snapshots "
-                                 "on the host: engine.host_reputation_pair_sums")
-            if self.L > self.reputation_max_side:
-                raise ValueError(f"reputation_max_d: the device sums lattices up to side {self.reputation_max_side}, "
-                                 f"L = {self.L} (sum snapshots on the host: engine.host_reputation_pair_sums)")
-            if not 0 <= rp_d <= self.L // 2:
-                raise ValueError(f"reputation_max_d must lie in 0 .. L // 2 = {self.L // 2}, got {rp_d}")
-        every = int(clusters_every)
-        if every < 0:
-            raise ValueError("clusters_every must be >= 0")
-        co_every = int(correlations_every)
-        if co_every < 0:
-            raise ValueError("correlations_every must be >= 0")
-        co_d = self.L // 2 if correlations_max_d is None else int(correlations_max_d)
-        if co_every and not 0 <= co_d <= self.L // 2:
-            raise ValueError(f"correlations_max_d must lie in 0 .. L // 2 = {self.L // 2}, got {co_d}")
-        if co_every and self.L > self.correlations_max_side:
-            raise ValueError(f"correlations_every: the device counts lattices up to side "
-                             f"{self.correlations_max_side}, L = {self.L} (count snapshots on the host: "
-                             f"engine.host_pair_counts)")
-        if every and self.L > self.clusters_max_side:
-            raise ValueError(f"clusters_every: the device labels lattices up to side {self.clusters_max_side}, "
-                             f"L = {self.L} (label snapshots on the host: engine.host_cluster_sizes)")
-        if every and (self.cl_rec is None or (every, bool(clusters_periodic)) != (self.cl_every, self.cl_periodic)):
-            # a run continued with the same settings keeps its record and its iterations
-            self.cl_rec = torch.zeros((self.R, self.T + 2, 3), dtype=torch.int32, device=self.dev)
-            self.cl_every, self.cl_periodic, self._cl_t0 = every, bool(clusters_periodic), self.t
-        if co_every and (self.co_rec is None or (co_every, co_d) != (self.co_every, self.co_max_d)):
-            # one row per recorded iteration t0, t0 + k, ... <= T (a continued run keeps its record)
-            rows = max(1, (self.T - self.t) // co_every + 1)
-            self.co_rec = torch.zeros((self.R, rows, 2 * (co_d + 1)), dtype=torch.int32, device=self.dev)
-            self.co_every, self.co_max_d, self._co_t0 = co_every, co_d, self.t
-        if rp_every and (self.rp_hist_rec is None or (rp_every, rp_bins, rp_d) != (self.rp_every, self.rp_bins, self.rp_max_d)):
-            rows = max(1, (self.T - self.t) // rp_every + 1)
-            self.rp_hist_rec = torch.zeros((self.R, rows, 2 * rp_bins), dtype=torch.int32, device=self.dev)
-            self.rp_pair_rec = (None if rp_d is None else
-                                torch.zeros((self.R, rows, 2 * (rp_d + 1) + 1), dtype=torch.int64, device=self.dev))
-            self.rp_edges = self._reputation_edges(rp_bins)
-            self.rp_every, self.rp_bins, self.rp_max_d, self._rp_t0 = rp_every, rp_bins, rp_d, self.t
+        In-run records (records.KINDS): *_every = k > 0 records the state at t = t0, t0+k, ... (t0 the
+        iteration the run starts at) on each replica group's own stream between the step launches of
+        t-1 and t -- a turn boundary there, no host sync; the stop-flag copies stay `chunk` iterations
+        apart -- one row per recorded iteration.  A run continued with the same settings keeps its
+        record, changed settings start a new one at the current t; every setting is checked
+        (ValueError) before anything is allocated or enqueued; with 0 nothing else is enqueued.
+          clusters_every: spgg_clusters of S_t (number of cooperator clusters, largest cluster, C-D
+            bonds; clusters_periodic: wrapped lattice); read with cluster_histories().
+          correlations_every: spgg_correlations of S_t, the cooperator pair counts at the distances
+            0 .. correlations_max_d (None: L // 2); read with correlation_histories().
+          reputation_every: spgg_reputation_hist of (S_t, R_t), the joint histogram strategy x bin
+            (reputation_bins bins over each replica's R_min .. R_max, the reference's edges); with
+            reputation_max_d also spgg_reputation_pairs, the pair sums of the int8 reputation plane at
+            the distances 0 .. reputation_max_d (not on an f64-reputation engine or above
+            reputation_max_side); read with reputation_histories()."""
+        asked = {"clusters": (clusters_every, clusters_periodic), "correlations": (correlations_every, correlations_max_d),
+                 "reputation": (reputation_every, reputation_bins, reputation_max_d)}
+        keys = {name: KINDS[name].validate(self, *a) for name, a in asked.items()}   # (before any allocation)
+        active = [self._record(name, key) for name, key in keys.items() if key[0]]
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -906,18 +740,12 @@ class BatchEngine:
         pending = []   # (event, slot) of the stop-flag copies in flight (<= 2: this turn's, the last one's)
         turn = 0
         done = False
-        t_rec0 = self._cl_t0 if every else 0   # the record's iterations: t_rec0, t_rec0 + every, ...
-        t_co0 = self._co_t0 if co_every else 0
-        t_rp0 = self._rp_t0 if rp_every else 0
         check_at = self.t + chunk  # the stop flags are copied every `chunk` iterations and at stops
         with torch.cuda.stream(loop):
             while self.t <= self.T and not done:
-                if every and (self.t - t_rec0) % every == 0:
-                    self._record_clusters(self.t)
-                if co_every and (self.t - t_co0) % co_every == 0:
-                    self._record_correlations(self.t)
-                if rp_every and (self.t - t_rp0) % rp_every == 0:
-                    self._record_reputation(self.t)
+                for rec in active:
+                    if rec.due(self.t):
+                        rec.write(self, self.t)
                 if self.t in stops:
                     self._capture(self.t, snapshots and self.t in SNAPSHOT_ITERS,
                                   png and (self.t - 1) in PNG_ITERS)
@@ -925,18 +753,11 @@ class BatchEngine:
                     done = self._note_stops(self.stop_iter.cpu().numpy())
                     if done:
                         break
-                nxt = min([s for s in stops if s > self.t] + [check_at, self.T + 1])
-                if every:
-                    nxt = min(nxt, self.t + every - (self.t - t_rec0) % every)
-                if co_every:
-                    nxt = min(nxt, self.t + co_every - (self.t - t_co0) % co_every)
-                if rp_every:
-                    nxt = min(nxt, self.t + rp_every - (self.t - t_rp0) % rp_every)
-                self.step(nxt - self.t)
+                self.step(next_boundary(self.t, stops, check_at, self.T + 1, active) - self.t)
                 if progress:
                     progress(self.t - 1)
                 if self.t < check_at and self.t <= self.T and self.t not in stops:
-                    continue       # a turn boundary of the cluster / pair-count / reputation record only
+                    continue       # a turn boundary of a record only
                 check_at = self.t + chunk
                 slot, turn = turn & 1, turn + 1
                 flags[slot].copy_(self.stop_iter, non_blocking=True)
@@ -1013,20 +834,43 @@ class BatchEngine:
             self.lib.spgg_payoff(g["ctx"], int(t), self.P_buf[g["r0"]].data_ptr(), s), g["ctx"], "spgg_payoff"))
         return self.P_buf.cpu().numpy().reshape(self.R, self.L, self.L)
 
-    # -- clusters ------------------------------------------------------------
-    def _clusters(self, t, periodic, sizes, rec, row, stride):
-        """Enqueue spgg_clusters of S_t on every group's stream: sizes (R, n) int32 or None,
-        the records into rec[k].view(-1)[row:row + 3] (stride int32 between replicas)."""
+    # -- observables: the final-state getters and the in-run records ----------
+    def _observe(self, fn, t, args, out, row=0):
+        """Enqueue the observable ABI call fn(ctx, t, *args, out, stride, stream) of the state at iteration t
+        on every group's stream: replica k's values into out[k].view(-1)[row:] (the stride between replicas
+        and the element size are out's).  A tensor among args is passed as the group's replica slice of it."""
+        stride, size = out[0].numel(), out.element_size()
         def one(g, s):
             r0 = g["r0"]
-            C.check(self.lib.spgg_clusters(
-                g["ctx"], int(t), int(bool(periodic)), sizes[r0].data_ptr() if sizes is not None else None,
-                rec.data_ptr() + 4 * (r0 * stride + row), stride, s), g["ctx"], "spgg_clusters")
+            a = [x[r0].data_ptr() if isinstance(x, torch.Tensor) else x for x in args]
+            C.check(fn(g["ctx"], int(t), *a, out.data_ptr() + size * (r0 * stride + row), stride, s),
+                    g["ctx"], fn.__name__)
         self._enqueue(one)
 
-    def _record_clusters(self, t):
-        """The in-run record of S_t into row t of cl_rec (run(clusters_every=...))."""
-        self._clusters(t, self.cl_periodic, None, self.cl_rec, 3 * t, (self.T + 2) * 3)
+    def _record(self, name, key):
+        """The in-run Record `name` (records.KINDS) with the validated settings `key`: the one a run
+        with the same settings left, or a new one that starts at the current iteration."""
+        rec = self.records.get(name)
+        if rec is None or rec.key != key:
+            rec = self.records[name] = KINDS[name](key[0], self.t, self.T, key)
+            rec.plan = rec.calls(self)
+            rec.out = [torch.zeros((self.R, rec.rows, w), dtype=getattr(torch, dt), device=self.dev)
+                       for _fn, _args, w, dt in rec.plan]
+        return rec
+
+    def _histories(self, name, what):
+        if name not in self.records:
+            raise ValueError(f"{what} with k > 0 first")
+        return self.records[name].histories(self)
+
+    def _final(self, key, fn, args, width, dtype=torch.int32):
+        """The (R, width) host array of one observable call on the final state, all replicas at
+        once (one call per replica group), cached until the engine steps again."""
+        if key not in self._final_cache:
+            out = torch.empty((self.R, width), dtype=dtype, device=self.dev)
+            self._observe(fn, self.t, args, out)
+            self._final_cache[key] = out.cpu().numpy().astype(np.int64, copy=False)
+        return self._final_cache[key]
 
     def cluster_sizes(self, k, periodic: bool = False) -> np.ndarray:
         """int64 sizes of replica k's cooperator clusters in the state final_state(k) returns, in
@@ -1038,54 +882,23 @@ class BatchEngine:
         periodic = bool(periodic)
         if self.L > self.clusters_max_side:
             return host_cluster_sizes(self.final_state(k)[2], periodic)
-        if periodic not in self._cl_cache:
-            if getattr(self, "_cl_sizes", None) is None:
-                self._cl_sizes = torch.empty((self.R, self.n), dtype=torch.int32, device=self.dev)
-                self._cl_final = torch.empty((self.R, 3), dtype=torch.int32, device=self.dev)
-            self._clusters(self.t, periodic, self._cl_sizes, self._cl_final, 0, 3)
-            flat = self._cl_sizes.view(-1)
+        if ("sizes", periodic) not in self._final_cache:
+            sizes = torch.empty((self.R, self.n), dtype=torch.int32, device=self.dev)
+            count = self._final(("cluster_record", periodic), self.lib.spgg_clusters, (int(periodic), sizes), 3)[:, 0]
+            flat = sizes.view(-1)
             vals = flat[flat > 0].cpu().numpy().astype(np.int64)   # compacted on the device
-            count = self._cl_final[:, 0].cpu().numpy()
             if np.any(count < 0):
                 raise C.SpggError(f"spgg_clusters: replicas {np.nonzero(count < 0)[0].tolist()} ran into the "
                                   f"labelling's pass cap ({C.CLUSTERS_MAX_PASSES})")
-            self._cl_cache[periodic] = np.split(vals, np.cumsum(count)[:-1])
-        return self._cl_cache[periodic][k]
+            self._final_cache["sizes", periodic] = np.split(vals, np.cumsum(count)[:-1])
+        return self._final_cache["sizes", periodic][k]
 
     def cluster_histories(self):
         """Per replica, the in-run cluster record of run(clusters_every=k): cluster_history_iters
-        (the observed iterations t <= last_iteration, so a replica absorbed at s keeps the record
-        of S_s if s was observed), cluster_count_history, largest_cluster_history and
+        (the recorded iterations t <= last_iteration, so a replica absorbed at s keeps the record
+        of S_s if s was recorded), cluster_count_history, largest_cluster_history and
         cd_bond_history (C-D bonds of the wrapped lattice), all int64."""
-        if not self.cl_every or self.cl_rec is None:
-            raise ValueError("cluster_histories: run(clusters_every=k) with k > 0 first")
-        rec = self.cl_rec.cpu().numpy().astype(np.int64)
-        out = []
-        for k in range(self.R):
-            its = np.arange(self._cl_t0, self.last_iteration(k) + 1, self.cl_every, dtype=np.int64)
-            r = rec[k, its]
-            if np.any(r[:, 0] < 0):
-                raise C.SpggError(f"spgg_clusters: replica {k} ran into the labelling's pass cap "
-                                  f"({C.CLUSTERS_MAX_PASSES}) at iterations {its[r[:, 0] < 0].tolist()}")
-            out.append(dict(cluster_history_iters=its, cluster_count_history=r[:, 0].copy(),
-                            largest_cluster_history=r[:, 1].copy(), cd_bond_history=r[:, 2].copy()))
-        return out
-
-    # -- pair correlations ---------------------------------------------------
-    def _correlations(self, t, max_d, out, row, stride):
-        """Enqueue spgg_correlations of S_t on every group's stream: replica k's 2 * (max_d + 1)
-        counts into out.view(-1)[k * stride + row:] (row, stride in int32)."""
-        def one(g, s):
-            C.check(self.lib.spgg_correlations(
-                g["ctx"], int(t), int(max_d), out.data_ptr() + 4 * (g["r0"] * stride + row), stride, s),
-                g["ctx"], "spgg_correlations")
-        self._enqueue(one)
-
-    def _record_correlations(self, t):
-        """The in-run record of S_t into its row of co_rec (run(correlations_every=...))."""
-        width = 2 * (self.co_max_d + 1)
-        self._correlations(t, self.co_max_d, self.co_rec, (t - self._co_t0) // self.co_every * width,
-                           self.co_rec.shape[1] * width)
+        return self._histories("clusters", "cluster_histories: run(clusters_every=k)")
 
     def pair_counts(self, k, max_d: Optional[int] = None) -> np.ndarray:
         """int64 (2, D+1) cooperator pair counts of replica k in the state final_state(k) returns,
@@ -1099,30 +912,14 @@ class BatchEngine:
             raise ValueError(f"pair_counts: max_d must lie in 0 .. L // 2 = {self.L // 2}, got {max_d}")
         if self.L > self.correlations_max_side:
             return host_pair_counts(self.final_state(k)[2], D)
-        if D not in self._co_cache:
-            out = torch.empty((self.R, 2 * (D + 1)), dtype=torch.int32, device=self.dev)
-            self._correlations(self.t, D, out, 0, 2 * (D + 1))
-            self._co_cache[D] = out.cpu().numpy().astype(np.int64).reshape(self.R, 2, D + 1)
-        return self._co_cache[D][k].copy()
+        return self._final(("pair_counts", D), self.lib.spgg_correlations, (D,), 2 * (D + 1))[k].reshape(2, D + 1).copy()
 
     def correlation_histories(self):
         """Per replica, the in-run pair-count record of run(correlations_every=k):
-        correlation_history_iters (the recorded iterations t <= last_iteration, so a replica
-        absorbed at s keeps the record of S_s if s was recorded), pair_count_rows_history and
+        correlation_history_iters (as cluster_history_iters), pair_count_rows_history and
         pair_count_cols_history, int64 (m, D+1)."""
-        if not self.co_every or self.co_rec is None:
-            raise ValueError("correlation_histories: run(correlations_every=k) with k > 0 first")
-        D = self.co_max_d
-        rec = self.co_rec.cpu().numpy().astype(np.int64)
-        out = []
-        for k in range(self.R):
-            its = np.arange(self._co_t0, self.last_iteration(k) + 1, self.co_every, dtype=np.int64)
-            r = rec[k, :len(its)]
-            out.append(dict(correlation_history_iters=its, pair_count_rows_history=r[:, :D + 1].copy(),
-                            pair_count_cols_history=r[:, D + 1:].copy()))
-        return out
+        return self._histories("correlations", "correlation_histories: run(correlations_every=k)")
 
-    # -- reputation record ---------------------------------------------------
     def _reputation_edges(self, bins, edges=None):
         """Device f64 (R, bins + 1) edges: each replica's reference edges over its R_min .. R_max,
         or the given ones for every replica."""
@@ -1134,34 +931,6 @@ class BatchEngine:
                 raise ValueError(f"reputation edges: {bins + 1} ascending values, got shape {e.shape}")
             e = np.broadcast_to(e, (self.R, bins + 1))
         return torch.from_numpy(np.ascontiguousarray(e)).to(self.dev)
-
-    def _reputation_hist(self, t, bins, edges, out, row, stride):
-        """Enqueue spgg_reputation_hist of (S_t, R_t) on every group's stream: replica k's 2 * bins
-        counts into out.view(-1)[k * stride + row:] (row, stride in int32)."""
-        def one(g, s):
-            C.check(self.lib.spgg_reputation_hist(
-                g["ctx"], int(t), int(bins), edges.data_ptr() + 8 * g["r0"] * (bins + 1),
-                out.data_ptr() + 4 * (g["r0"] * stride + row), stride, s), g["ctx"], "spgg_reputation_hist")
-        self._enqueue(one)
-
-    def _reputation_pairs(self, t, max_d, out, row, stride):
-        """Enqueue spgg_reputation_pairs of R_t on every group's stream: replica k's
-        2 * (max_d + 1) + 1 sums into out.view(-1)[k * stride + row:] (row, stride in int64)."""
-        def one(g, s):
-            C.check(self.lib.spgg_reputation_pairs(
-                g["ctx"], int(t), int(max_d), out.data_ptr() + 8 * (g["r0"] * stride + row), stride, s),
-                g["ctx"], "spgg_reputation_pairs")
-        self._enqueue(one)
-
-    def _record_reputation(self, t):
-        """The in-run record of (S_t, R_t) into its row of the records (run(reputation_every=...))."""
-        row = (t - self._rp_t0) // self.rp_every
-        width = 2 * self.rp_bins
-        self._reputation_hist(t, self.rp_bins, self.rp_edges, self.rp_hist_rec, row * width,
-                              self.rp_hist_rec.shape[1] * width)
-        if self.rp_pair_rec is not None:
-            width = 2 * (self.rp_max_d + 1) + 1
-            self._reputation_pairs(t, self.rp_max_d, self.rp_pair_rec, row * width, self.rp_pair_rec.shape[1] * width)
 
     def reputation_histogram(self, k, bins: int = 20, edges=None) -> np.ndarray:
         """int64 (2, bins) joint histogram strategy x reputation bin of replica k in the state
@@ -1175,12 +944,9 @@ class BatchEngine:
         if not 1 <= bins <= 256:
             raise ValueError(f"reputation_histogram: bins must lie in 1 .. 256, got {bins}")
         key = ("hist", bins, None if edges is None else np.asarray(edges, dtype=np.float64).tobytes())
-        if key not in self._rp_cache:
-            e = self._reputation_edges(bins, edges)
-            out = torch.empty((self.R, 2 * bins), dtype=torch.int32, device=self.dev)
-            self._reputation_hist(self.t, bins, e, out, 0, 2 * bins)
-            self._rp_cache[key] = out.cpu().numpy().astype(np.int64).reshape(self.R, 2, bins)
-        return self._rp_cache[key][k].copy()
+        if key not in self._final_cache:
+            self._final(key, self.lib.spgg_reputation_hist, (bins, self._reputation_edges(bins, edges)), 2 * bins)
+        return self._final_cache[key][k].reshape(2, bins).copy()
 
     def reputation_pair_sums(self, k, max_d: Optional[int] = None):
         """(sum, rows, cols) of replica k's reputation plane in the state final_state(k) returns,
@@ -1200,13 +966,7 @@ class BatchEngine:
             s = int(self.stopped[k])
             cur = (s - 1) & 1 if s else self.last_iteration(k) & 1
             return host_reputation_pair_sums(self.Rep[cur, k].cpu().numpy().reshape(self.L, self.L), D)
-        key = ("pairs", D)
-        if key not in self._rp_cache:
-            width = 2 * (D + 1) + 1
-            out = torch.empty((self.R, width), dtype=torch.int64, device=self.dev)
-            self._reputation_pairs(self.t, D, out, 0, width)
-            self._rp_cache[key] = out.cpu().numpy()
-        r = self._rp_cache[key][k]
+        r = self._final(("pairs", D), self.lib.spgg_reputation_pairs, (D,), 2 * (D + 1) + 1, torch.int64)[k]
         return int(r[0]), r[1:D + 2].copy(), r[D + 2:].copy()
 
     def reputation_histories(self):
@@ -1215,25 +975,7 @@ class BatchEngine:
         reputation_hist_history int64 (m, 2, bins) and reputation_bin_edges f64 (bins + 1,); with
         reputation_max_d also reputation_sum_history (m,), reputation_pair_rows_history and
         reputation_pair_cols_history (m, D+1), int64 in units of reputation_unit (squared)."""
-        if not self.rp_every or self.rp_hist_rec is None:
-            raise ValueError("reputation_histories: run(reputation_every=k) with k > 0 first")
-        B, D = self.rp_bins, self.rp_max_d
-        rec = self.rp_hist_rec.cpu().numpy().astype(np.int64)
-        pairs = None if self.rp_pair_rec is None else self.rp_pair_rec.cpu().numpy()
-        edges = self.rp_edges.cpu().numpy()
-        out = []
-        for k in range(self.R):
-            its = np.arange(self._rp_t0, self.last_iteration(k) + 1, self.rp_every, dtype=np.int64)
-            d = dict(reputation_history_iters=its,
-                     reputation_hist_history=rec[k, :len(its)].reshape(len(its), 2, B).copy(),
-                     reputation_bin_edges=edges[k].copy())
-            if pairs is not None:
-                r = pairs[k, :len(its)]
-                d.update(reputation_sum_history=r[:, 0].copy(), reputation_pair_rows_history=r[:, 1:D + 2].copy(),
-                         reputation_pair_cols_history=r[:, D + 2:].copy(),
-                         reputation_unit=np.float64(self.rep_units[k]))
-            out.append(d)
-        return out
+        return self._histories("reputation", "reputation_histories: run(reputation_every=k)")
 
     def finalize_history(self):
         """Derived history slots (payoff sums, w_P*P, w_rep*rr, reward over D) of every

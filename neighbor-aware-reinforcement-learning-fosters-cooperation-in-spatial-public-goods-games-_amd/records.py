@@ -1,0 +1,257 @@
+"""The in-run device records of BatchEngine.run and the host-side models of what they hold.
+
+A `Record` is one stream of observations of the running lattice: every `every` iterations from `t0`
+on, one ABI call per device tensor writes one row.  The kinds (KINDS) differ only in their settings,
+calls and datasets.  The schedule is plain Python; the engine allocates and enqueues (_observe).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib as C
+
+
+def next_boundary(t, stops, check_at, end, records=()):
+    """The iteration at which the turn of BatchEngine.run that starts at t ends: the next snapshot /
+    PNG stop, the next stop-flag copy (check_at), the run's end (T + 1) or the next row of an active
+    record, whichever comes first."""
+    return min([s for s in stops if s > t] + [check_at, end] + [r.next_due(t) for r in records])
+
+
+def _every(name, value) -> int:
+    value = int(value)
+    if value < 0:
+        raise ValueError(f"{name} must be >= 0")
+    return value
+
+
+class Record:
+    """A record of the iterations t0, t0 + every, ... <= T: `key` its settings (every first), `out`
+    its device tensors, each (R, rows, width) with one row per recorded iteration, `plan` the (ABI
+    function, its scalar arguments, width, dtype) of the call that fills each (a kind's calls)."""
+
+    def __init__(self, every, t0, T, key=()):
+        self.every, self.t0, self.key = int(every), int(t0), key
+        self.rows = max(1, (T - self.t0) // self.every + 1)
+        self.plan, self.out = [], []
+
+    def due(self, t) -> bool:
+        return (t - self.t0) % self.every == 0
+
+    def next_due(self, t) -> int:
+        """The first recorded iteration after t."""
+        return t + self.every - (t - self.t0) % self.every
+
+    def row(self, t) -> int:
+        return (t - self.t0) // self.every
+
+    def iters(self, last) -> np.ndarray:
+        return np.arange(self.t0, last + 1, self.every, dtype=np.int64)
+
+    def write(self, eng, t):
+        """Enqueue the record of iteration t into its row of every tensor."""
+        row = self.row(t)
+        for (fn, args, width, _), out in zip(self.plan, self.out):
+            eng._observe(fn, t, args, out, row * width)
+
+    def histories(self, eng):
+        """Per replica, the datasets of the recorded iterations t <= last_iteration (so a replica
+        absorbed at s keeps the record of S_s if s was recorded)."""
+        host = [o.cpu().numpy().astype(np.int64, copy=False) for o in self.out]
+        its = [self.iters(eng.last_iteration(k)) for k in range(eng.R)]
+        return [self.datasets(eng, k, its[k], *[h[k, :len(its[k])] for h in host]) for k in range(eng.R)]
+
+
+class Clusters(Record):
+    """spgg_clusters of S_t: (clusters, largest cluster, C-D bonds) int32; key (every, periodic)."""
+
+    @staticmethod
+    def validate(eng, every, periodic):
+        every = _every("clusters_every", every)
+        if every and eng.L > eng.clusters_max_side:
+            raise ValueError(f"clusters_every: the device labels lattices up to side {eng.clusters_max_side}, "
+                             f"L = {eng.L} (label snapshots on the host: engine.host_cluster_sizes)")
+        return every, bool(periodic)
+
+    def calls(self, eng):
+        return [(eng.lib.spgg_clusters, (int(self.key[1]), None), 3, "int32")]
+
+    def datasets(self, eng, k, its, r):
+        if np.any(r[:, 0] < 0):
+            raise C.SpggError(f"spgg_clusters: replica {k} ran into the labelling's pass cap "
+                              f"({C.CLUSTERS_MAX_PASSES}) at iterations {its[r[:, 0] < 0].tolist()}")
+        return dict(cluster_history_iters=its, cluster_count_history=r[:, 0].copy(),
+                    largest_cluster_history=r[:, 1].copy(), cd_bond_history=r[:, 2].copy())
+
+
+class Correlations(Record):
+    """spgg_correlations of S_t: D + 1 row then D + 1 column pair counts, int32; key (every, D)."""
+
+    @staticmethod
+    def validate(eng, every, max_d):
+        every = _every("correlations_every", every)
+        D = eng.L // 2 if max_d is None else int(max_d)
+        if every and not 0 <= D <= eng.L // 2:
+            raise ValueError(f"correlations_max_d must lie in 0 .. L // 2 = {eng.L // 2}, got {D}")
+        if every and eng.L > eng.correlations_max_side:
+            raise ValueError(f"correlations_every: the device counts lattices up to side {eng.correlations_max_side}, "
+                             f"L = {eng.L} (count snapshots on the host: engine.host_pair_counts)")
+        return every, D
+
+    def calls(self, eng):
+        return [(eng.lib.spgg_correlations, (self.key[1],), 2 * (self.key[1] + 1), "int32")]
+
+    def datasets(self, eng, k, its, r):
+        D = self.key[1]
+        return dict(correlation_history_iters=its, pair_count_rows_history=r[:, :D + 1].copy(),
+                    pair_count_cols_history=r[:, D + 1:].copy())
+
+
+class Reputation(Record):
+    """spgg_reputation_hist of (S_t, R_t): 2 x bins counts, int32, over each replica's reference edges; with
+    D not None also spgg_reputation_pairs of the int8 plane: sum, D + 1 row and D + 1 column sums,
+    int64; key (every, bins, D)."""
+
+    @staticmethod
+    def validate(eng, every, bins, max_d):
+        every, bins = _every("reputation_every", every), int(bins)
+        D = None if max_d is None else int(max_d)
+        if every and not 1 <= bins <= 256:
+            raise ValueError(f"reputation_bins must lie in 1 .. 256, got {bins}")
+        if every and D is not None:
+            if not eng.rep_int8:
+                raise ValueError("reputation_max_d: the pair sums are exact integers of the int8 reputation path; "
+                                 "this engine holds f64 reputation (non-dyadic gains or bounds) -- sum snapshots "
+                                 "on the host: engine.host_reputation_pair_sums")
+            if eng.L > eng.reputation_max_side:
+                raise ValueError(f"reputation_max_d: the device sums lattices up to side {eng.reputation_max_side}, "
+                                 f"L = {eng.L} (sum snapshots on the host: engine.host_reputation_pair_sums)")
+            if not 0 <= D <= eng.L // 2:
+                raise ValueError(f"reputation_max_d must lie in 0 .. L // 2 = {eng.L // 2}, got {D}")
+        return every, bins, D
+
+    def calls(self, eng):
+        _, bins, D = self.key
+        pairs = [] if D is None else [(eng.lib.spgg_reputation_pairs, (D,), 2 * (D + 1) + 1, "int64")]
+        return [(eng.lib.spgg_reputation_hist, (bins, eng._reputation_edges(bins)), 2 * bins, "int32")] + pairs
+
+    def datasets(self, eng, k, its, h, r=None):
+        _, bins, D = self.key
+        d = dict(reputation_history_iters=its, reputation_hist_history=h.reshape(len(its), 2, bins).copy(),
+                 reputation_bin_edges=reputation_bin_edges(eng.reps[k].R_min, eng.reps[k].R_max, bins))
+        if r is not None:
+            d.update(reputation_sum_history=r[:, 0].copy(), reputation_pair_rows_history=r[:, 1:D + 2].copy(),
+                     reputation_pair_cols_history=r[:, D + 2:].copy(), reputation_unit=np.float64(eng.rep_units[k]))
+        return d
+
+
+KINDS = {"clusters": Clusters, "correlations": Correlations, "reputation": Reputation}
+
+
+def host_cluster_sizes(S, periodic: bool = False) -> np.ndarray:
+    """int64 sizes of the 4-connected cooperator (S == 0) clusters of one lattice in label order
+    (ascending smallest raster index), on the host: scipy.ndimage.label (spgg.py:631-633);
+    periodic merges its labels across the two seams.  The path of lattices above the device
+    labelling's supported side (spgg_clusters_max_side)."""
+    from scipy.ndimage import label
+    lab, k = label(np.asarray(S) == 0)
+    counts = np.bincount(lab.ravel(), minlength=k + 1).astype(np.int64)
+    if not periodic or k == 0:
+        return counts[1:]
+    root = np.arange(k + 1)
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+
+    for a, b in list(zip(lab[0], lab[-1])) + list(zip(lab[:, 0], lab[:, -1])):
+        if a and b:
+            ra, rb = find(a), find(b)
+            if ra != rb:
+                root[max(ra, rb)] = min(ra, rb)   # the label met first in raster order stays
+    owner = np.array([find(a) for a in range(k + 1)])
+    merged = np.bincount(owner, weights=counts, minlength=k + 1).astype(np.int64)
+    return merged[(owner == np.arange(k + 1)) & (np.arange(k + 1) > 0)]
+
+
+def host_pair_counts(S, max_d=None) -> np.ndarray:
+    """int64 (2, D+1) cooperator pair counts of one lattice on the host, D = max_d (None: L // 2):
+    with c = 1 where bit 0 of S is 0, [0, d] = sum(c & roll(c, -d, axis=1)) (pairs d apart along
+    a row) and [1, d] = sum(c & roll(c, -d, axis=0)) (along a column), periodic.  What
+    spgg_correlations counts on the device, and the path of lattices above its supported side
+    (spgg_correlations_max_side)."""
+    c = (np.asarray(S).astype(np.int64) & 1) == 0
+    L = c.shape[0]
+    D = L // 2 if max_d is None else int(max_d)
+    if c.shape != (L, L) or D < 0 or D > L // 2:
+        raise ValueError(f"host_pair_counts: a square lattice and 0 <= max_d <= L // 2, got {c.shape}, {max_d}")
+    out = np.empty((2, D + 1), dtype=np.int64)
+    for d in range(D + 1):
+        out[0, d] = np.count_nonzero(c & np.roll(c, -d, axis=1))
+        out[1, d] = np.count_nonzero(c & np.roll(c, -d, axis=0))
+    return out
+
+
+def correlation_function(rows, cols, n):
+    """Connected two-point function of the cooperator field from pair counts (any leading axes,
+    the distance last): G(d) = (rows + cols) / (2 n) - (rows[..., 0] / n)^2, n = L * L cells --
+    the direction-averaged <c(x) c(x + d)> minus the squared cooperation rate."""
+    rows, cols = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
+    rho = rows[..., :1] / n
+    return (rows + cols) / (2.0 * n) - rho * rho
+
+
+def correlation_length(G) -> float:
+    """Distance at which g = G / G[0] first falls to 1/e: the first d >= 1 with g(d) <= 1/e,
+    linearly interpolated between d - 1 and d.  nan if G[0] == 0 (an absorbed lattice), inf if g
+    never falls that far within the given distances."""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 1 or G.size == 0:
+        raise ValueError("correlation_length: a one-dimensional G(d), d = 0 ..")
+    if G[0] == 0:
+        return float("nan")
+    g = G / G[0]
+    below = np.nonzero(g[1:] <= 1.0 / np.e)[0]
+    if below.size == 0:
+        return float("inf")
+    d = int(below[0]) + 1
+    return float(d - 1 + (g[d - 1] - 1.0 / np.e) / (g[d - 1] - g[d]))
+
+
+def reputation_bin_edges(R_min, R_max, bins: int = 20) -> np.ndarray:
+    """The bins + 1 edges np.histogram(x, bins=bins, range=(R_min, R_max)) uses -- with bins = 20
+    the reference's rep_bins_* datasets (spgg.py:399)."""
+    return np.histogram_bin_edges(np.empty(0), int(bins), (float(R_min), float(R_max)))
+
+
+def host_reputation_pair_sums(K, max_d=None):
+    """(sum, rows, cols) of one reputation lattice on the host, D = max_d (None: L // 2): sum =
+    K.sum(), rows[d] = sum(K * roll(K, -d, axis=1)), cols[d] = sum(K * roll(K, -d, axis=0)) for
+    d = 0 .. D, periodic.  Integer input (the int8 plane, in units of rep_unit) is summed in int64
+    and is what spgg_reputation_pairs gives on the device, exactly; float input (R itself, the f64
+    reputation path) gives the same sums in float64, rounded and so not exact.  The path of
+    f64-reputation engines and of lattices above spgg_reputation_max_side."""
+    K = np.asarray(K)
+    L = K.shape[0]
+    D = L // 2 if max_d is None else int(max_d)
+    if K.shape != (L, L) or D < 0 or D > L // 2:
+        raise ValueError(f"host_reputation_pair_sums: a square lattice and 0 <= max_d <= L // 2, got {K.shape}, {max_d}")
+    K = K.astype(np.int64 if np.issubdtype(K.dtype, np.integer) else np.float64)
+    rows, cols = np.empty(D + 1, dtype=K.dtype), np.empty(D + 1, dtype=K.dtype)
+    for d in range(D + 1):
+        rows[d] = np.sum(K * np.roll(K, -d, axis=1))
+        cols[d] = np.sum(K * np.roll(K, -d, axis=0))
+    return K.sum(), rows, cols
+
+
+def reputation_correlation_function(sum, rows, cols, n, unit):
+    """Connected two-point function of the reputation field from pair sums (any leading axes, the
+    distance last; sum without the distance axis): unit^2 * ((rows + cols) / (2 n) - (sum / n)^2),
+    n = L * L cells, unit the replica's rep_unit (1 for sums of R itself) -- the direction-averaged
+    <R(x) R(x + d)> minus the squared mean.  correlation_length applies to it as it stands."""
+    rows, cols = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
+    mean = np.asarray(sum, dtype=np.float64)[..., None] / n
+    return float(unit) ** 2 * ((rows + cols) / (2.0 * n) - mean * mean)
+

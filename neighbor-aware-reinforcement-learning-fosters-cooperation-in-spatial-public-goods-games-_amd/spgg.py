@@ -28,29 +28,42 @@ def sum_position_and_neighbors(A_):
     return _sum5(A_)
 
 
+def _count(v):
+    return int(v or 0)
+
+
+# The in-run record options: class attributes of SPGG (not constructor arguments; the sweep takes
+# them among its model overrides), name -> (default, BatchEngine.run keyword argument, conversion).
+# *_every = k > 0: also record S_t (and R_t) at t = 1, 1+k, ... on the device and write the record as
+# more datasets after the reference's own; 0: the reference's file.
+RECORD_OPTIONS = {
+    # the cooperator clusters (count, largest, C-D bonds: CLUSTER_DATASETS); _periodic: they wrap
+    # with the lattice (the final cluster_sizes dataset never does: spgg.py:631)
+    "cluster_history_every": (0, "clusters_every", _count),
+    "cluster_history_periodic": (False, "clusters_periodic", bool),
+    # the cooperator pair counts along rows and columns at the distances 0 .. correlation_max_distance
+    # (None: L // 2; CORRELATION_DATASETS)
+    "correlation_history_every": (0, "correlations_every", _count),
+    "correlation_max_distance": (None, "correlations_max_d", lambda v: v),
+    # the joint histogram strategy x reputation bin (reputation_history_bins bins over R_min .. R_max)
+    # and, with reputation_max_distance not None, the pair sums of the int8 reputation plane at the
+    # distances 0 .. reputation_max_distance (REPUTATION_DATASETS)
+    "reputation_history_every": (0, "reputation_every", _count),
+    "reputation_history_bins": (20, "reputation_bins", int),
+    "reputation_max_distance": (None, "reputation_max_d", lambda v: v),
+}
+
+
+def record_run_kwargs(values):
+    """BatchEngine.run's record keyword arguments from option values (a mapping; absent: default)."""
+    return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in RECORD_OPTIONS.items()}
+
+
 class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
-    # k > 0: also record the cooperator clusters of S_t (count, largest, C-D bonds) at
-    # t = 1, 1+k, ... on the device and write them as four more datasets (CLUSTER_DATASETS);
-    # 0: the reference's file.  The clusters of the record wrap with the lattice if
-    # cluster_history_periodic (the final cluster_sizes dataset never does: spgg.py:631).
-    cluster_history_every = 0
-    cluster_history_periodic = False
-    # k > 0: also record the cooperator pair counts of S_t along rows and columns at the
-    # distances 0 .. correlation_max_distance (None: L // 2) at t = 1, 1+k, ... on the device and
-    # write them as three more datasets (CORRELATION_DATASETS); 0: the reference's file.
-    correlation_history_every = 0
-    correlation_max_distance = None
-    # k > 0: also record the joint histogram strategy x reputation bin of (S_t, R_t)
-    # (reputation_history_bins bins over R_min .. R_max) at t = 1, 1+k, ... on the device and, with
-    # reputation_max_distance not None, the pair sums of the int8 reputation plane at the distances
-    # 0 .. reputation_max_distance; written as more datasets (REPUTATION_DATASETS); 0: the
-    # reference's file.
-    reputation_history_every = 0
-    reputation_history_bins = 20
-    reputation_max_distance = None
+    # (the RECORD_OPTIONS are class attributes too, set at their defaults below the class)
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -157,18 +170,11 @@ class SPGG:
         snapshots_dir = os.path.join(self.folder, 'plots', 'snapshots') if self.folder else 'snapshots'
         os.makedirs(snapshots_dir, exist_ok=True)
         try:
-            every = int(self.cluster_history_every or 0)
-            co_every = int(self.correlation_history_every or 0)
-            rp_every = int(self.reputation_history_every or 0)
-            eng.run(snapshots=True, png=self.save_png, clusters_every=every,
-                    clusters_periodic=bool(self.cluster_history_periodic), correlations_every=co_every,
-                    correlations_max_d=self.correlation_max_distance, reputation_every=rp_every,
-                    reputation_bins=int(self.reputation_history_bins), reputation_max_d=self.reputation_max_distance)
+            records = record_run_kwargs({name: getattr(self, name) for name in RECORD_OPTIONS})
+            eng.run(snapshots=True, png=self.save_png, **records)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (host above its supported side)
-            cluster_hist = eng.cluster_histories()[0] if every > 0 else None
-            correlation_hist = eng.correlation_histories()[0] if co_every > 0 else None
-            reputation_hist = eng.reputation_histories()[0] if rp_every > 0 else None
+            record_hists = {arg: h and h[0] for arg, h in record_histories(eng, records).items()}
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -199,13 +205,15 @@ class SPGG:
         # the datasets last: the reference fills its file after the loop, so a write
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
-                       clusters=clusters, cluster_hist=cluster_hist, correlation_hist=correlation_hist,
-                       reputation_hist=reputation_hist)
+                       clusters=clusters, **record_hists)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
         return (np.sum(S_coop) / (L * L), np.sum(S_def) / (L * L), np.mean(P))
 
+
+for _name, (_default, _kw, _conv) in RECORD_OPTIONS.items():
+    setattr(SPGG, _name, _default)
 
 
 HISTORY_DATASETS = ("it_records_final", "epsilon_history_final", "rep_avg_history_final",
@@ -226,6 +234,20 @@ CORRELATION_DATASETS = ("correlation_history_iters", "pair_count_rows_history", 
 REPUTATION_DATASETS = ("reputation_history_iters", "reputation_hist_history", "reputation_bin_edges",
                        "reputation_sum_history", "reputation_pair_rows_history", "reputation_pair_cols_history",
                        "reputation_unit")
+OPTIONAL_DATASETS = REPUTATION_DATASETS[3:]
+FLOAT_DATASETS = ("reputation_bin_edges", "reputation_unit")   # the other record datasets are int64
+
+
+# per record kind: run()'s keyword that switches it on, the engine's getter, write_datasets' keyword, its datasets
+RECORD_KINDS = (("clusters_every", "cluster_histories", "cluster_hist", CLUSTER_DATASETS),
+                ("correlations_every", "correlation_histories", "correlation_hist", CORRELATION_DATASETS),
+                ("reputation_every", "reputation_histories", "reputation_hist", REPUTATION_DATASETS))
+
+
+def record_histories(eng, run_kwargs):
+    """write_datasets' keyword -> the engine's per-replica histories of each record the run took
+    (run_kwargs: record_run_kwargs' result), None for the others -- whose getter is not asked."""
+    return {arg: getattr(eng, getter)() if run_kwargs[on] > 0 else None for on, getter, arg, _names in RECORD_KINDS}
 
 
 def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
@@ -272,18 +294,11 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
         data_file.create_dataset("rep_bins_final", data=bins)
         data_file.create_dataset("cluster_sizes", data=cluster_sizes(S) if clusters is None
                                  else np.asarray(clusters, dtype=np.int64))
-        if cluster_hist is not None:
-            for name in CLUSTER_DATASETS:
-                data_file.create_dataset(name, data=np.asarray(cluster_hist[name], dtype=np.int64))
-        if correlation_hist is not None:
-            for name in CORRELATION_DATASETS:
-                data_file.create_dataset(name, data=np.asarray(correlation_hist[name], dtype=np.int64))
-        if reputation_hist is not None:
-            for name in REPUTATION_DATASETS:
-                if name in reputation_hist:
-                    float_valued = name in ("reputation_bin_edges", "reputation_unit")
+        for (_on, _getter, _arg, names), h in zip(RECORD_KINDS, (cluster_hist, correlation_hist, reputation_hist)):
+            for name in names if h is not None else ():
+                if name in h or name not in OPTIONAL_DATASETS:
                     data_file.create_dataset(name, data=np.asarray(
-                        reputation_hist[name], dtype=np.float64 if float_valued else np.int64))
+                        h[name], dtype=np.float64 if name in FLOAT_DATASETS else np.int64))
 
 
 def track_positions(L):

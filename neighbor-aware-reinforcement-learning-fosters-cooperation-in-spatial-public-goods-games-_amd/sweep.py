@@ -188,25 +188,25 @@ def run_one_experiment(params: Tuple, **model_overrides) -> Tuple[Tuple, Tuple[f
     folder = get_folder_name(*p8)
     make_folders(folder)
     kw = dict(RUNNER_MODEL, **model_overrides)
-    every = int(kw.pop("cluster_history_every", 0) or 0)   # class attributes of the drop-in,
-    periodic = bool(kw.pop("cluster_history_periodic", False))   # not constructor arguments
-    co_every = int(kw.pop("correlation_history_every", 0) or 0)
-    co_max_d = kw.pop("correlation_max_distance", None)
-    rp_every = int(kw.pop("reputation_history_every", 0) or 0)
-    rp_bins = int(kw.pop("reputation_history_bins", 20))
-    rp_max_d = kw.pop("reputation_max_distance", None)
+    records = pop_record_options(kw)
     spgg = SPGG(r=r, alpha=alpha, influence_factor=kappa, use_second_order=so,
                 reward_weight_payoff=w_p, rep_gain_C=gain, state_representation=state,
                 algorithm=algorithm, **kw)
     spgg.folder = folder
-    spgg.cluster_history_every, spgg.cluster_history_periodic = every, periodic
-    spgg.correlation_history_every, spgg.correlation_max_distance = co_every, co_max_d
-    spgg.reputation_history_every, spgg.reputation_history_bins = rp_every, rp_bins
-    spgg.reputation_max_distance = rp_max_d
+    for name, value in records.items():
+        setattr(spgg, name, value)
     coop, _def, _p = spgg.run(os.path.join(folder, "data", "experiment_data.h5"))
     rep_mean = spgg.rep_avg_history[-1] if spgg.rep_avg_history else 0
     print(_done_line(p8))
     return params, (coop, rep_mean)
+
+
+def pop_record_options(kw):
+    """Take the in-run record options (spgg.RECORD_OPTIONS: class attributes of the drop-in, not
+    constructor arguments nor RUNNER_MODEL keys) out of the model overrides kw: name -> value,
+    absent ones at their defaults."""
+    from .spgg import RECORD_OPTIONS
+    return {name: conv(kw.pop(name, default)) for name, (default, _run_kw, conv) in RECORD_OPTIONS.items()}
 
 
 def _replica(p8, kw, seed):
@@ -232,19 +232,10 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
     `np.random.seed()` (spgg.py:98)."""
     import torch
     from .engine import BatchEngine, reference_init
-    from .spgg import _write_pngs, track_positions, write_datasets
+    from .spgg import _write_pngs, record_histories, record_run_kwargs, track_positions, write_datasets
     from .algorithms import canonical_name
     kw = dict(RUNNER_MODEL, **model_overrides)
-    # the in-run cluster record (SPGG.cluster_history_every / _periodic): not constructor arguments
-    every = int(kw.pop("cluster_history_every", 0) or 0)
-    periodic = bool(kw.pop("cluster_history_periodic", False))
-    # the in-run pair-count record (SPGG.correlation_history_every / correlation_max_distance)
-    co_every = int(kw.pop("correlation_history_every", 0) or 0)
-    co_max_d = kw.pop("correlation_max_distance", None)
-    # the in-run reputation record (SPGG.reputation_history_every / _bins / reputation_max_distance)
-    rp_every = int(kw.pop("reputation_history_every", 0) or 0)
-    rp_bins = int(kw.pop("reputation_history_bins", 20))
-    rp_max_d = kw.pop("reputation_max_distance", None)
+    records = record_run_kwargs(pop_record_options(kw))
     L, iters = int(kw["L"]), int(kw["iterations"])
     p8s = [unpack(p) for p in param_list]
     seeds = list(seeds) if seeds is not None else [None] * len(p8s)
@@ -267,22 +258,16 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
         eng = BatchEngine(L, max(iters, 1), reps, use_second_order=so, state_representation=state,
                           rng="mt19937", init=inits, algorithm=alg)
         try:
-            eng.run(snapshots=True, png=save_png, progress=progress, clusters_every=every,
-                    clusters_periodic=periodic, correlations_every=co_every, correlations_max_d=co_max_d,
-                    reputation_every=rp_every, reputation_bins=rp_bins, reputation_max_d=rp_max_d)
+            eng.run(snapshots=True, png=save_png, progress=progress, **records)
             hist = eng.histories()
-            cl_hist = eng.cluster_histories() if every > 0 else None
-            co_hist = eng.correlation_histories() if co_every > 0 else None
-            rp_hist = eng.reputation_histories() if rp_every > 0 else None
+            record_hists = record_histories(eng, records)
             for k, i in enumerate(idx):
                 folder = get_folder_name(*p8s[i])
                 make_folders(folder)
                 _q, R, S = eng.final_state(k)
                 write_datasets(os.path.join(folder, "data", "experiment_data.h5"), hist[k], eng.snapshots[k],
                                S, R, kw["R_min"], kw["R_max"], track_positions(L),
-                               clusters=eng.cluster_sizes(k), cluster_hist=cl_hist[k] if cl_hist else None,
-                               correlation_hist=co_hist[k] if co_hist else None,
-                               reputation_hist=rp_hist[k] if rp_hist else None)
+                               clusters=eng.cluster_sizes(k), **{arg: h and h[k] for arg, h in record_hists.items()})
                 if save_png and eng.png_frames[k]:
                     _write_pngs(eng.png_frames[k], os.path.join(folder, "plots", "snapshots"))
                 coop = float(np.sum(S == 0)) / (L * L)

@@ -47,7 +47,7 @@ def _check_engine(eng, planes, names):
             assert got.dtype == np.int64 and got.shape == want.shape, (names[k], periodic, got.shape, want.shape)
             assert np.array_equal(got, want), (names[k], periodic)
             assert np.array_equal(eng.final_state(k)[2], S & 1)
-        rec = eng._cl_final.cpu().numpy()   # the record of the same launch
+        rec = eng._final_cache["cluster_record", periodic]   # the record of the same launch
         for k, S in enumerate(planes):
             assert tuple(rec[k]) == K.expected_record(S, periodic), (names[k], periodic, rec[k])
 
@@ -138,6 +138,7 @@ def test_in_run_record():
                        mt=[eng.mt_state_host(k) for k in range(3)], last=[eng.last_iteration(k) for k in range(3)])
             if every:
                 out["clusters"] = eng.cluster_histories()
+                out["rec_rows"] = eng.records["clusters"].out[0].shape[1]
             return out
         finally:
             eng.close()
@@ -150,6 +151,7 @@ def test_in_run_record():
         for every in (1, 7):
             got = run(every, periodic)
             _assert_histories(got["clusters"], planes, last, every, periodic)
+            assert got["rec_rows"] == (T - 1) // every + 1   # one row per recorded iteration, not T + 2
             # the record does not disturb the run
             for k in range(3):
                 for a, b in zip(got["final"][k], plain["final"][k]):

@@ -171,7 +171,7 @@ def test_in_run_record():
                        mt=[eng.mt_state_host(k) for k in range(3)], last=[eng.last_iteration(k) for k in range(3)])
             if every:
                 out["corr"] = eng.correlation_histories()
-                out["rec_rows"] = eng.co_rec.shape[1]
+                out["rec_rows"] = eng.records["correlations"].out[0].shape[1]
                 out["final_counts"] = [eng.pair_counts(k) for k in range(3)]
             if clusters_every:
                 out["clusters"] = eng.cluster_histories()

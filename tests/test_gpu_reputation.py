@@ -176,7 +176,7 @@ def test_f64_reputation_path():
         assert "f64" in eng.lib.spgg_last_error(eng.ctx).decode()
         with pytest.raises(ValueError, match="f64"):
             eng.run(snapshots=False, reputation_every=1, reputation_max_d=2)
-        assert eng.t == 1 and eng.rp_hist_rec is None   # nothing was enqueued
+        assert eng.t == 1 and "reputation" not in eng.records   # nothing was enqueued
         eng.run(snapshots=False, reputation_every=5, reputation_bins=20)
         assert not out.cpu().numpy().any()
         hist = eng.reputation_histories()
@@ -261,7 +261,7 @@ def test_in_run_record():
                        mt=[eng.mt_state_host(k) for k in range(3)], last=[eng.last_iteration(k) for k in range(3)])
             if every:
                 out["rep"] = eng.reputation_histories()
-                out["rec_rows"] = eng.rp_hist_rec.shape[1]
+                out["rec_rows"] = eng.records["reputation"].out[0].shape[1]
                 out["final_hist"] = [eng.reputation_histogram(k) for k in range(3)]
                 out["final_pairs"] = [eng.reputation_pair_sums(k) for k in range(3)]
             if others:
@@ -318,11 +318,12 @@ def test_record_from_a_later_iteration_and_continued():
         kw = dict(snapshots=False, reputation_every=every, reputation_max_d=3)
         eng.step(5)
         eng.run(**kw)
-        rec, pairs = eng.rp_hist_rec, eng.rp_pair_rec
+        record = eng.records["reputation"]
+        rec, pairs = record.out
         assert rec.shape[1] == (T - 6) // every + 1
         first = eng.reputation_histories()
         eng.run(**kw)
-        assert eng.rp_hist_rec is rec and eng.rp_pair_rec is pairs
+        assert eng.records["reputation"] is record and record.out[0] is rec and record.out[1] is pairs
         hist = eng.reputation_histories()
     finally:
         eng.close()

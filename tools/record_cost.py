@@ -1,0 +1,258 @@
+"""What the device records cost (profiles/{clusters,correlations,reputation}/README.txt).
+
+    python tools/record_cost.py --record clusters|correlations|reputation [--repeats 5] [--iters 10000]
+                                [--legs LEG,LEG,...]
+
+Every variant runs in a fresh process (this driver never touches the GPU) and reports the median of
+its repeats.  Legs (default: all of the record's, in this order):
+  clusters      final  the final cluster sizes of the cfg3 batch (105 x L=200) at t ~ 500: the device
+                       path (spgg_clusters + compaction of the size planes on the device + copy)
+                       against the host path it replaces (copy of each replica's S + scipy label)
+                call   device time of one spgg_clusters round over every replica (HIP events over 100
+                       rounds) at cfg3's and cfg4's shapes: record only / with the size planes,
+                       walls / periodic
+  correlations  call   the same for spgg_correlations at cfg3's, cfg4's (max_d = 100) and cfg5's
+                       (max_d = 500) shapes
+                host   the same counts by engine.host_pair_counts on host copies of the planes
+  reputation    hist   the same for spgg_reputation_hist (20 bins, the reference's edges)
+                pairs  the same for spgg_reputation_pairs, max_d as for correlations
+                host   both by the host path: copies of the S and R planes, np.histogram per strategy
+                       and engine.host_reputation_pair_sums (np.roll)
+  every record  run    the whole cfg3 run (BatchEngine.run, MT19937, as bench.full_run times it) with
+                       the record every {0, 16, 1} iterations (max_d = 100, 20 bins)
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MAX_D = {"cfg3": 100, "cfg4": 100, "cfg5": 500}
+BINS = 20
+SHAPES = ["cfg3", "cfg4", "cfg5"]
+
+
+def _engine_at(config, t, T, rng="philox"):
+    import torch
+    import bench
+    from spgg_amd.engine import BatchEngine
+    _desc, L, M2, state, reps = bench.workload(config, 0)
+    eng = BatchEngine(L, T, reps, use_second_order=M2, state_representation=state, rng=rng)
+    eng.step(t)
+    eng.flush()
+    torch.cuda.synchronize()
+    eng.all_stopped()
+    return eng
+
+
+def _timed_rounds(eng, a, call):
+    """us per round of call(group, stream) over every group on one stream: the kernels' own time."""
+    import torch
+    cur = torch.cuda.current_stream(eng.dev)
+    rounds, out = 100, []
+    for _ in range(a.repeats + 1):   # (the first repeat warms up)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(cur)
+        for _ in range(rounds):
+            for g in eng.groups:
+                rc = call(g, cur.cuda_stream)
+                assert rc == 0, rc
+        e1.record(cur)
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) * 1e3 / rounds)
+    return out[1:]
+
+
+def _final_planes(eng, buf):
+    """(R, L, L) host copies of the plane of `buf` (eng.S / eng.Rep) that final_state reads, per replica."""
+    planes = [buf[b].cpu().numpy().reshape(eng.R, eng.L, eng.L) for b in (0, 1)]
+    stop = [int(s) for s in eng.stopped]
+    return [planes[(s - 1) & 1 if s else (eng.t - 1) & 1][k] for k, s in enumerate(stop)]
+
+
+def leg_final(a):
+    import torch
+    from spgg_amd import spgg
+    eng = _engine_at("cfg3", 500, 600)
+    try:
+        out = []
+        for _ in range(a.repeats + 1):   # (the first repeat warms up: allocation, scipy import)
+            eng.step(1)                  # one more iteration: the engine forgets its cached sizes
+            torch.cuda.synchronize()
+            eng.all_stopped()
+            t0 = time.perf_counter()
+            if a.variant == "device":
+                n = sum(len(eng.cluster_sizes(k)) for k in range(eng.R))
+            else:
+                n = sum(len(spgg.cluster_sizes(S & 1)) for S in _final_planes(eng, eng.S))
+            out.append(time.perf_counter() - t0)
+        return {"leg": "final", "variant": a.variant, "replicas": eng.R, "clusters": n, "seconds": out[1:]}
+    finally:
+        eng.close()
+
+
+def leg_call(a):
+    import numpy as np
+    import torch
+    if a.record == "clusters":
+        config, sizes, periodic = a.variant.split(":")
+    else:
+        config = a.variant
+    D = MAX_D[config]
+    eng = _engine_at(config, *((500, 600) if a.record == "clusters" else (200, 300)))
+    try:
+        def buf(width, dtype=torch.int32):
+            return torch.zeros((eng.R, width), dtype=dtype, device=eng.dev)
+        info = {} if a.record == "clusters" else {"L": eng.L}
+        if a.record == "clusters":
+            out_buf, planes = buf(3), buf(eng.n) if sizes == "sizes" else None
+            us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_clusters(
+                g["ctx"], eng.t, int(periodic), planes[g["r0"]].data_ptr() if planes is not None else None,
+                out_buf[g["r0"]].data_ptr(), 3, s))
+        elif a.record == "correlations":
+            out_buf = buf(2 * (D + 1))
+            us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_correlations(
+                g["ctx"], eng.t, D, out_buf[g["r0"]].data_ptr(), 2 * (D + 1), s))
+            got = out_buf.cpu().numpy()
+            assert (got[:, 0] == got[:, D + 1]).all()   # rows[0] == cols[0]
+            info["max_d"] = D
+        elif a.child == "hist":
+            from spgg_amd.engine import reputation_bin_edges
+            edges = torch.from_numpy(np.stack([reputation_bin_edges(p.R_min, p.R_max, BINS) for p in eng.reps])).to(eng.dev)
+            out_buf = buf(2 * BINS)
+            us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_reputation_hist(
+                g["ctx"], eng.t, BINS, edges[g["r0"]].data_ptr(), out_buf[g["r0"]].data_ptr(), 2 * BINS, s))
+            assert (out_buf.cpu().numpy().sum(axis=1) == eng.L * eng.L).all()   # every cell lies within R_min .. R_max
+            info.update(bins=BINS, int8=bool(eng.rep_int8))
+        else:
+            width = 2 * (D + 1) + 1
+            out_buf = buf(width, torch.int64)
+            us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_reputation_pairs(
+                g["ctx"], eng.t, D, out_buf[g["r0"]].data_ptr(), width, s))
+            got = out_buf.cpu().numpy()
+            assert (got[:, 1] == got[:, D + 2]).all()   # rows[0] == cols[0]
+            info["max_d"] = D
+        return {"leg": a.child, "variant": a.variant, **info, "replicas": eng.R, "groups": eng.G, "us_per_round": us}
+    finally:
+        eng.close()
+
+
+def leg_host(a):
+    import numpy as np
+    from spgg_amd.engine import host_pair_counts, host_reputation_pair_sums
+    D = MAX_D[a.variant]
+    eng = _engine_at(a.variant, 200, 300)
+    try:
+        res = {"leg": "host", "variant": a.variant, "L": eng.L, "max_d": D, "replicas": eng.R}
+        if a.record == "correlations":
+            device = [eng.pair_counts(k, D) for k in range(eng.R)]
+            out = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                host = [host_pair_counts(S, D) for S in _final_planes(eng, eng.S)]
+                out.append(time.perf_counter() - t0)
+            same = all((h == d).all() for h, d in zip(host, device))
+            return {**res, "equals_device": bool(same), "seconds": out}
+        dev_hist = [eng.reputation_histogram(k, BINS) for k in range(eng.R)]
+        dev_pairs = [eng.reputation_pair_sums(k, D) for k in range(eng.R)]
+        t_hist, t_pairs = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            S, Rp = _final_planes(eng, eng.S), _final_planes(eng, eng.Rep)
+            t1 = time.perf_counter()
+            hists = []
+            for k, p in enumerate(eng.reps):
+                x, coop = Rp[k] * eng.rep_units[k], (S[k] & 1) == 0
+                hists.append(np.stack([np.histogram(x[coop], bins=BINS, range=(p.R_min, p.R_max))[0],
+                                       np.histogram(x[~coop], bins=BINS, range=(p.R_min, p.R_max))[0]]))
+            t2 = time.perf_counter()
+            pairs = [host_reputation_pair_sums(Rp[k], D) for k in range(eng.R)]
+            t3 = time.perf_counter()
+            t_hist.append(t2 - t0)
+            t_pairs.append((t1 - t0) + (t3 - t2))
+        same = all((h == d).all() for h, d in zip(hists, dev_hist)) and all(
+            int(h[0]) == d[0] and (h[1] == d[1]).all() and (h[2] == d[2]).all() for h, d in zip(pairs, dev_pairs))
+        return {**res, "equals_device": bool(same), "hist_seconds": t_hist, "seconds": t_pairs}
+    finally:
+        eng.close()
+
+
+def leg_run(a):
+    import torch
+    import bench
+    from spgg_amd.engine import BatchEngine
+    every = int(a.variant)
+    run_kw = {"clusters": dict(clusters_every=every),
+              "correlations": dict(correlations_every=every, correlations_max_d=MAX_D["cfg3"]),
+              "reputation": dict(reputation_every=every, reputation_bins=BINS,
+                                 reputation_max_d=MAX_D["cfg3"] if every else None)}[a.record]
+    _desc, L, M2, state, reps = bench.workload("cfg3", 0)
+    out = []
+    for _ in range(a.repeats + 1):
+        eng = BatchEngine(L, a.iters, reps, use_second_order=M2, state_representation=state, rng="mt19937")
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.run(snapshots=False, **run_kw)
+            torch.cuda.synchronize()
+            out.append(time.perf_counter() - t0)
+            if every and a.record == "clusters":
+                eng.cluster_histories()   # (raises on a capped labelling)
+        finally:
+            eng.close()
+    info = {} if a.record == "clusters" else {"max_d": MAX_D["cfg3"]}
+    return {"leg": "run", "variant": a.variant, "iterations": a.iters, **info, "seconds": out[1:]}
+
+
+RUN = (leg_run, ["0", "16", "1"])
+LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
+                     "call": (leg_call, [f"{c}:{s}:{p}" for c in ("cfg3", "cfg4") for s in ("record", "sizes")
+                                         for p in (0, 1)]),
+                     "run": (leg_run, ["0", "1", "16"])},
+        "correlations": {"call": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN},
+        "reputation": {"hist": (leg_call, SHAPES), "pairs": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--record", required=True, choices=sorted(LEGS))
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=10000)
+    ap.add_argument("--legs", default=None)
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--variant", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    legs = LEGS[a.record]
+    if a.child:
+        print("RESULT " + json.dumps(legs[a.child][0](a)), flush=True)
+        return 0
+    width = 16 if a.record == "clusters" else 6
+    for leg in (a.legs.split(",") if a.legs else legs):
+        for variant in legs[leg][1]:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--record", a.record, "--child", leg,
+                                "--variant", variant, "--repeats", str(a.repeats), "--iters", str(a.iters)],
+                               capture_output=True, text=True, timeout=600)
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+            if r.returncode or not line:
+                print(f"{leg} {variant}: failed rc={r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", flush=True)
+                return 1   # nothing more is started after a failed leg
+            d = json.loads(line[0][7:])
+            for key, unit in (("us_per_round", "us"), ("hist_seconds", "s (hist)"), ("seconds", "s")):
+                vals = d.get(key)
+                if not vals:
+                    continue
+                print(f"{leg:5s} {variant:{width}s} median {statistics.median(vals):.6g} {unit}  "
+                      f"min {min(vals):.6g} max {max(vals):.6g}  n={len(vals)}  "
+                      + " ".join(f"{k}={v}" for k, v in d.items()
+                                 if k not in ("seconds", "hist_seconds", "us_per_round", "leg", "variant")),
+                      flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
