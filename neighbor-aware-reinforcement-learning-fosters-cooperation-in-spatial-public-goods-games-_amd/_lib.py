@@ -33,6 +33,11 @@ ST_GC0, ST_NMD_POS, ST_NMD_POS2, ST_SUM_PCT = 12, 18, 19, 20
 ST_SUMQ, ST_SUMQ_C, ST_SUMQ_D, ST_GMAX = 21, 25, 29, 33
 NSTAT = 34
 
+# dwell record row layout (enum in spgg_abi.h)
+DW_NEVER, DW_NEVER_C, DW_SAME, DW_BOTH_C, DW_NCOOP, DW_FLIPS, DW_COOP_TIME, DW_AGE0 = range(8)
+DWELL_AGE_BINS = 27
+DWELL_SLOTS = DW_AGE0 + 2 * DWELL_AGE_BINS   # 61
+
 EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create", "spgg_set_params",
             "spgg_bind", "spgg_step", "spgg_step_groups", "spgg_flush", "spgg_draw", "spgg_payoff", "spgg_tile_shape",
             "spgg_destroy", "spgg_draw_planes", "spgg_pub_doubles", "spgg_stat_stripes",
@@ -40,7 +45,8 @@ EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create
             "spgg_mt_chains", "spgg_mt_jump_poly", "spgg_stream_create", "spgg_stream_destroy",
             "spgg_status", "spgg_persistent", "spgg_clusters", "spgg_clusters_max_side",
             "spgg_correlations", "spgg_correlations_max_side", "spgg_reputation_hist",
-            "spgg_reputation_pairs", "spgg_reputation_max_side")
+            "spgg_reputation_pairs", "spgg_reputation_max_side", "spgg_dwell_bind", "spgg_dwell_reset",
+            "spgg_dwell_record", "spgg_dwell_fields")
 # test-only entry points (include/spgg_test.h): exported by the library, not part of the product ABI
 TEST_EXPORTED = ("spgg_test_set_error",)
 
@@ -134,6 +140,14 @@ def load(path: str | None = None):
         lib.spgg_reputation_pairs.argtypes = [vp, i32, i32, vp, ctypes.c_int64, vp]
         lib.spgg_reputation_max_side.restype = ctypes.c_int
         lib.spgg_reputation_max_side.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.spgg_dwell_bind.restype = ctypes.c_int
+        lib.spgg_dwell_bind.argtypes = [vp, vp, vp]
+        lib.spgg_dwell_reset.restype = ctypes.c_int
+        lib.spgg_dwell_reset.argtypes = [vp, i32, vp]
+        lib.spgg_dwell_record.restype = ctypes.c_int
+        lib.spgg_dwell_record.argtypes = [vp, i32, vp, ctypes.c_int64, vp]
+        lib.spgg_dwell_fields.restype = ctypes.c_int
+        lib.spgg_dwell_fields.argtypes = [vp, i32, vp, ctypes.c_int64, vp]
         lib.spgg_persistent.restype = ctypes.c_int
         lib.spgg_persistent.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         lib.spgg_destroy.restype = ctypes.c_int

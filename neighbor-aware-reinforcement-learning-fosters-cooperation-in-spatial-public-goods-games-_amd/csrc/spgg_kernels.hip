@@ -47,6 +47,7 @@
 #include "spgg_clusters.h"
 #include "spgg_correlations.h"
 #include "spgg_reputation.h"
+#include "spgg_dwell.h"
 
 using namespace spgg;
 
@@ -2729,6 +2730,12 @@ struct spgg_ctx {
   int persist_capacity = 0;      // workgroups the device holds at once (occupancy x CUs)
   uint32_t* d_bar = nullptr;
   uint32_t bar_base = 0;         // barrier rounds of this run's earlier persistent launches
+  // the strategy dwell record (spgg_dwell_*): the caller's buffers; armed by spgg_dwell_reset, from
+  // then on step_seg enqueues its launch after the step launch of every iteration >= dwell_t_ref
+  uint32_t* dwell_words = nullptr;
+  uint8_t* dwell_ref = nullptr;
+  bool dwell_armed = false;
+  int dwell_t_ref = 0;
   std::string err;
 };
 
@@ -3496,6 +3503,7 @@ static int step_setup(spgg_ctx* c) {
 
 static int step_begin(spgg_ctx* c, int32_t t0, int32_t n_steps, hipStream_t s) {
   if (t0 == 1) c->params_moved = false;  // a new run
+  if (t0 == 1 && c->dwell_t_ref != 1) c->dwell_armed = false;  // a dwell reference of an earlier run is dropped
   const bool mt = c->cfg.rng_mode == SPGG_RNG_MT19937;
   int rc = step_setup(c);
   if (rc) return rc;
@@ -3539,6 +3547,8 @@ static void step_seg(spgg_ctx* c, int t, int t1, int32_t t0, hipStream_t s) {
   if (timing != 1) {
     if (t1 > t) launch_persist(c, t, t1, s);
     else launch_step(c, t, 0, s);
+    if (c->dwell_armed && t >= c->dwell_t_ref)   // (never with persistent launches: spgg_dwell_bind)
+      spgg_dw::launch_step(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t, c->dwell_words, s);
   }
   if (mt && (t1 % K == 0 || t1 == T)) (void)hipEventRecord(c->step_done[((t1 - 1) / K) & 1], s);
 }
@@ -3716,6 +3726,57 @@ int spgg_reputation_pairs(spgg_ctx* c, int32_t t, int32_t max_d, int64_t* out, i
                         c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, max_d, reinterpret_cast<long long*>(out), out_stride,
                         reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_reputation_pairs launch");
+}
+
+int spgg_dwell_bind(spgg_ctx* c, uint32_t* words, uint8_t* ref) {
+  if (!c || !words != !ref) return fail(c, SPGG_E_ARG, "spgg_dwell_bind: both buffers or neither");
+  if (words && c->persist)
+    return fail(c, SPGG_E_STATE, "spgg_dwell_bind: the context steps in persistent launches (spgg_persistent): there is "
+                                 "no launch boundary between two iterations for the dwell launch");
+  if ((reinterpret_cast<uintptr_t>(words) & 3) != 0)
+    return fail(c, SPGG_E_ARG, "spgg_dwell_bind: the words buffer must be 4-byte aligned");
+  c->dwell_words = words;
+  c->dwell_ref = ref;
+  c->dwell_armed = false;
+  c->dwell_t_ref = 0;
+  return SPGG_OK;
+}
+
+int spgg_dwell_reset(spgg_ctx* c, int32_t t_ref, void* stream) {
+  if (const int rc = observable_check(c, "spgg_dwell_reset", true, false, t_ref)) return rc;
+  if (!c->dwell_words) return fail(c, SPGG_E_STATE, "spgg_dwell_reset before spgg_dwell_bind");
+  if (t_ref > c->cfg.iterations + 1) return fail(c, SPGG_E_ARG, "spgg_dwell_reset: t_ref beyond iterations + 1");
+  spgg_dw::launch_reset(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t_ref, c->dwell_words,
+                        c->dwell_ref, reinterpret_cast<hipStream_t>(stream));
+  c->dwell_armed = true;
+  c->dwell_t_ref = t_ref;
+  return hip_check(c, hipGetLastError(), "spgg_dwell_reset launch");
+}
+
+// The shared checks of the two dwell read-outs.
+static int dwell_check(spgg_ctx* c, const char* fn, const void* out, int32_t t, int64_t out_stride, int64_t need) {
+  if (const int rc = observable_check(c, fn, out, false, t)) return rc;
+  if (!c->dwell_armed) return fail(c, SPGG_E_STATE, std::string(fn) + ": no dwell record is armed (spgg_dwell_reset)");
+  if (t < c->dwell_t_ref || t > c->cfg.iterations + 1)
+    return fail(c, SPGG_E_ARG, std::string(fn) + ": t = " + std::to_string(t) + " outside t_ref = " +
+                                   std::to_string(c->dwell_t_ref) + " .. iterations + 1");
+  if (out_stride < need) return fail(c, SPGG_E_ARG, std::string(fn) + ": out_stride below " + std::to_string(need));
+  return SPGG_OK;
+}
+
+int spgg_dwell_record(spgg_ctx* c, int32_t t, int64_t* out, int64_t out_stride, void* stream) {
+  if (const int rc = dwell_check(c, "spgg_dwell_record", out, t, out_stride, SPGG_DWELL_SLOTS)) return rc;
+  spgg_dw::launch_record(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t, c->dwell_t_ref,
+                         c->dwell_words, c->dwell_ref, reinterpret_cast<long long*>(out), out_stride,
+                         reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_dwell_record launch");
+}
+
+int spgg_dwell_fields(spgg_ctx* c, int32_t t, int32_t* out, int64_t out_stride, void* stream) {
+  if (const int rc = dwell_check(c, "spgg_dwell_fields", out, t, out_stride, c ? 3 * (int64_t)c->n : 0)) return rc;
+  spgg_dw::launch_fields(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t, c->dwell_t_ref,
+                         c->dwell_words, out, out_stride, reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_dwell_fields launch");
 }
 
 int spgg_status(const spgg_ctx* c, uint32_t* flags) {

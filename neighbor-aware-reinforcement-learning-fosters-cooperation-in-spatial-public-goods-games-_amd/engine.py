@@ -32,6 +32,7 @@ import torch
 
 from . import _lib as C
 from .algorithms import canonical_name
+from .dwell import DWELL_SLOTS, Dwell
 from .records import (KINDS, next_boundary,  # noqa: F401  (the host models stay importable from here)
                       host_cluster_sizes, host_pair_counts, correlation_function, correlation_length,
                       reputation_bin_edges, host_reputation_pair_sums, reputation_correlation_function)
@@ -328,8 +329,9 @@ class BatchEngine:
         self.snapshots = [dict() for _ in range(self.R)]
         self.png_frames = [dict() for _ in range(self.R)]
         self._flushed = False
-        self.records = {}          # name (records.KINDS) -> the in-run Record of the last run that asked for it
+        self.records = {}          # name (records.KINDS, "dwell") -> the in-run Record of the last run that asked for it
         self._final_cache = {}     # final-state observables (cluster_sizes, pair_counts, ...) until the next step
+        self.dwell_t_ref = None    # the reference iteration of the strategy dwell record while it is tracked
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -698,7 +700,7 @@ class BatchEngine:
             progress: Optional[Callable[[int], None]] = None, clusters_every: int = 0,
             clusters_periodic: bool = False, correlations_every: int = 0,
             correlations_max_d: Optional[int] = None, reputation_every: int = 0,
-            reputation_bins: int = 20, reputation_max_d: Optional[int] = None):
+            reputation_bins: int = 20, reputation_max_d: Optional[int] = None, dwell_every: int = 0):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -723,11 +725,33 @@ class BatchEngine:
             (reputation_bins bins over each replica's R_min .. R_max, the reference's edges); with
             reputation_max_d also spgg_reputation_pairs, the pair sums of the int8 reputation plane at
             the distances 0 .. reputation_max_d (not on an f64-reputation engine or above
-            reputation_max_side); read with reputation_histories()."""
+            reputation_max_side); read with reputation_histories().
+        dwell_every = k > 0 also tracks the per-agent strategy dwell record (dwell_start at the run's
+        first iteration, the reference: one more launch after every step launch) and records its row
+        (spgg_dwell_record: persistence, autocorrelation, flips, cooperator time, strategy ages) on the
+        same schedule; read with dwell_histories().  A run continued with the same k keeps its record
+        and its reference, another k starts afresh at the current t, 0 stops the tracking of an
+        earlier run and drops its record; not on an engine that steps in persistent launches."""
         asked = {"clusters": (clusters_every, clusters_periodic), "correlations": (correlations_every, correlations_max_d),
                  "reputation": (reputation_every, reputation_bins, reputation_max_d)}
         keys = {name: KINDS[name].validate(self, *a) for name, a in asked.items()}   # (before any allocation)
+        dwell_every = int(dwell_every)
+        if dwell_every < 0:
+            raise ValueError("dwell_every must be >= 0")
+        if dwell_every and self.persistent:
+            raise ValueError("dwell_every: this engine steps in persistent launches, which have no launch "
+                             "boundary between two iterations for the dwell launch")
         active = [self._record(name, key) for name, key in keys.items() if key[0]]
+        if dwell_every:
+            rec = self.records.get("dwell")
+            if rec is None or rec.every != dwell_every or self.dwell_t_ref != rec.t0:
+                self.dwell_start()
+                rec = self.records["dwell"] = Dwell(dwell_every, self.t, self.T)
+                rec.plan = rec.calls(self)
+                rec.out = [torch.zeros((self.R, rec.rows, DWELL_SLOTS), dtype=torch.int64, device=self.dev)]
+            active.append(rec)
+        elif "dwell" in self.records:
+            self.dwell_stop()
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -976,6 +1000,70 @@ class BatchEngine:
         reputation_max_d also reputation_sum_history (m,), reputation_pair_rows_history and
         reputation_pair_cols_history (m, D+1), int64 in units of reputation_unit (squared)."""
         return self._histories("reputation", "reputation_histories: run(reputation_every=k)")
+
+    # -- the strategy dwell record (dwell.py; spgg_dwell_*) -------------------
+    def dwell_start(self):
+        """Start (or restart) tracking every agent's strategy changes with the current state S_t as
+        the reference: 12 bytes of device state per agent and one byte for the reference plane, one
+        more launch after every step launch from now on (step and run alike).  Not part of the
+        Infinity-Cache budget of the group planning."""
+        if self.persistent:
+            raise ValueError("dwell_start: this engine steps in persistent launches (no launch boundary "
+                             "between two iterations for the dwell launch)")
+        if self.dwell_t_ref is None:
+            self._dwell_words = torch.empty((self.R, self.n, 3), dtype=torch.int32, device=self.dev)
+            self._dwell_ref = torch.empty((self.R, self.n), dtype=torch.uint8, device=self.dev)
+            for g in self.groups:
+                C.check(self.lib.spgg_dwell_bind(g["ctx"], self._dwell_words[g["r0"]].data_ptr(),
+                                                 self._dwell_ref[g["r0"]].data_ptr()), g["ctx"], "spgg_dwell_bind")
+        t_ref = self.t
+        self._enqueue(lambda g, s: C.check(self.lib.spgg_dwell_reset(g["ctx"], t_ref, s), g["ctx"], "spgg_dwell_reset"))
+        self.dwell_t_ref = t_ref
+        self.records.pop("dwell", None)
+        self._final_cache = {}
+
+    def dwell_stop(self):
+        """Stop the tracking, free its device state and drop the in-run record."""
+        if self.dwell_t_ref is None:
+            return
+        torch.cuda.synchronize(self.dev)   # the groups' streams may still hold dwell launches
+        for g in self.groups:
+            C.check(self.lib.spgg_dwell_bind(g["ctx"], None, None), g["ctx"], "spgg_dwell_bind")
+        self._dwell_words = self._dwell_ref = None
+        self.dwell_t_ref = None
+        self.records.pop("dwell", None)
+        self._final_cache = {}
+
+    def _dwell_tracked(self, what):
+        if self.dwell_t_ref is None:
+            raise ValueError(f"{what}: dwell_start() or run(dwell_every=k) first")
+
+    def dwell_record(self) -> np.ndarray:
+        """int64 (R, DWELL_SLOTS) rows (spgg_abi.h: spgg_dwell_record) of every replica's current
+        state -- the state final_state returns; an absorbed replica's: of its absorbing iteration."""
+        self._dwell_tracked("dwell_record")
+        return self._final("dwell_record", self.lib.spgg_dwell_record, (), DWELL_SLOTS, torch.int64).copy()
+
+    def dwell_fields(self, k) -> dict:
+        """Replica k's per-agent fields of the current state, (L, L) each: flip_count and
+        strategy_age (int64; iterations the agent has held its strategy) and cooperation_frequency
+        (f64: the share of the states t_ref .. t in which it cooperated, one host division of the
+        device's exact count)."""
+        self._dwell_tracked("dwell_fields")
+        f = self._final("dwell_fields", self.lib.spgg_dwell_fields, (), 3 * self.n)[k].reshape(3, self.L, self.L)
+        s = int(self.stop_iter[k].item())   # (not self.stopped: as of the last host check of the stops)
+        t = max(s, self.dwell_t_ref) if s else self.t
+        return dict(flip_count=f[0].copy(), strategy_age=f[1].copy(),
+                    cooperation_frequency=f[2] / np.float64(t - self.dwell_t_ref + 1))
+
+    def dwell_histories(self):
+        """Per replica, the in-run dwell record of run(dwell_every=k) (dwell.DWELL_DATASETS):
+        dwell_history_iters (the recorded iterations t <= last_iteration), dwell_ref_iteration,
+        persistence_history (m, 2: never flipped, of them reference cooperators),
+        autocorrelation_history (m, 3: same as the reference, cooperator then and now, cooperators),
+        flip_total_history, cooperator_time_history (m,) and strategy_age_hist_history
+        (m, 2, DWELL_AGE_BINS), all int64."""
+        return self._histories("dwell", "dwell_histories: run(dwell_every=k)")
 
     def finalize_history(self):
         """Derived history slots (payoff sums, w_P*P, w_rep*rr, reward over D) of every

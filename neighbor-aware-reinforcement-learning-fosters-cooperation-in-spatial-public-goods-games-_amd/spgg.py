@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from . import algorithms as A
+from .dwell import DWELL_DATASETS, DWELL_FIELD_DATASETS
 from .engine import BatchEngine, InitState, ReplicaParams, SNAPSHOT_ITERS
 from .h5io import open_writer
 
@@ -54,6 +55,39 @@ RECORD_OPTIONS = {
 }
 
 
+# The strategy dwell record's options (dwell.py), class attributes of SPGG like the RECORD_OPTIONS but
+# a table of their own: the record is not one of records.KINDS.  name -> (default, conversion).
+# dwell_history_every = k > 0: track every agent's strategy changes from iteration 1 on and write the
+# DWELL_DATASETS (rows at t = 1, 1+k, ...) after the other records' datasets; dwell_fields: also the
+# per-agent DWELL_FIELD_DATASETS of the final state.
+DWELL_OPTIONS = {
+    "dwell_history_every": (0, _count),
+    "dwell_fields": (False, bool),
+}
+
+
+def dwell_option_values(values):
+    """(dwell_every, dwell_fields) from option values (a mapping; absent: default)."""
+    every, fields = (conv(values.get(name, default)) for name, (default, conv) in DWELL_OPTIONS.items())
+    if fields and not every:
+        raise ValueError("dwell_fields needs dwell_history_every > 0 (nothing is tracked otherwise)")
+    return every, fields
+
+
+def dwell_histories(eng, every, fields):
+    """write_datasets' dwell_hist of every replica of a run(dwell_every=every): the engine's
+    dwell_histories, with `fields` also the per-agent fields of the final state; None without."""
+    if not every:
+        return None
+    hist = eng.dwell_histories()
+    if fields:
+        for k, h in enumerate(hist):
+            f = eng.dwell_fields(k)
+            h.update({name: f[key] for name, key in zip(DWELL_FIELD_DATASETS, ("flip_count", "strategy_age",
+                                                                               "cooperation_frequency"))})
+    return hist
+
+
 def record_run_kwargs(values):
     """BatchEngine.run's record keyword arguments from option values (a mapping; absent: default)."""
     return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in RECORD_OPTIONS.items()}
@@ -63,7 +97,7 @@ class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
-    # (the RECORD_OPTIONS are class attributes too, set at their defaults below the class)
+    # (the RECORD_OPTIONS and DWELL_OPTIONS are class attributes too, set at their defaults below the class)
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -171,10 +205,12 @@ class SPGG:
         os.makedirs(snapshots_dir, exist_ok=True)
         try:
             records = record_run_kwargs({name: getattr(self, name) for name in RECORD_OPTIONS})
-            eng.run(snapshots=True, png=self.save_png, **records)
+            dwell_every, dwell_fields = dwell_option_values({name: getattr(self, name) for name in DWELL_OPTIONS})
+            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (host above its supported side)
             record_hists = {arg: h and h[0] for arg, h in record_histories(eng, records).items()}
+            dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -205,7 +241,7 @@ class SPGG:
         # the datasets last: the reference fills its file after the loop, so a write
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
-                       clusters=clusters, **record_hists)
+                       clusters=clusters, dwell_hist=dwell_hist and dwell_hist[0], **record_hists)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -213,6 +249,8 @@ class SPGG:
 
 
 for _name, (_default, _kw, _conv) in RECORD_OPTIONS.items():
+    setattr(SPGG, _name, _default)
+for _name, (_default, _conv) in DWELL_OPTIONS.items():
     setattr(SPGG, _name, _default)
 
 
@@ -251,7 +289,7 @@ def record_histories(eng, run_kwargs):
 
 
 def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
-                   cluster_hist=None, correlation_hist=None, reputation_hist=None):
+                   cluster_hist=None, correlation_hist=None, reputation_hist=None, dwell_hist=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
     the final state.  Shared by SPGG.run and the batched sweep runner.
@@ -261,7 +299,9 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
     as the CLUSTER_DATASETS after the reference's own; correlation_hist: the in-run pair-count
     record (BatchEngine.correlation_histories), written as the CORRELATION_DATASETS after those;
     reputation_hist: the in-run reputation record (BatchEngine.reputation_histories), written as
-    the REPUTATION_DATASETS it holds after those.
+    the REPUTATION_DATASETS it holds after those; dwell_hist: the in-run strategy dwell record
+    (BatchEngine.dwell_histories), written as the DWELL_DATASETS after those, then the
+    DWELL_FIELD_DATASETS it holds (int64; cooperation_frequency_final f64).
     The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
@@ -299,6 +339,10 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
                 if name in h or name not in OPTIONAL_DATASETS:
                     data_file.create_dataset(name, data=np.asarray(
                         h[name], dtype=np.float64 if name in FLOAT_DATASETS else np.int64))
+        for name in DWELL_DATASETS + DWELL_FIELD_DATASETS if dwell_hist is not None else ():
+            if name in dwell_hist or name in DWELL_DATASETS:
+                data_file.create_dataset(name, data=np.asarray(
+                    dwell_hist[name], dtype=np.float64 if name == "cooperation_frequency_final" else np.int64))
 
 
 def track_positions(L):

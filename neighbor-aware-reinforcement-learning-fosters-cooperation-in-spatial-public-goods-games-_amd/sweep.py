@@ -188,7 +188,7 @@ def run_one_experiment(params: Tuple, **model_overrides) -> Tuple[Tuple, Tuple[f
     folder = get_folder_name(*p8)
     make_folders(folder)
     kw = dict(RUNNER_MODEL, **model_overrides)
-    records = pop_record_options(kw)
+    records = dict(pop_record_options(kw), **pop_dwell_options(kw))
     spgg = SPGG(r=r, alpha=alpha, influence_factor=kappa, use_second_order=so,
                 reward_weight_payoff=w_p, rep_gain_C=gain, state_representation=state,
                 algorithm=algorithm, **kw)
@@ -207,6 +207,13 @@ def pop_record_options(kw):
     absent ones at their defaults."""
     from .spgg import RECORD_OPTIONS
     return {name: conv(kw.pop(name, default)) for name, (default, _run_kw, conv) in RECORD_OPTIONS.items()}
+
+
+def pop_dwell_options(kw):
+    """Take the strategy dwell record's options (spgg.DWELL_OPTIONS) out of the model overrides kw
+    the same way."""
+    from .spgg import DWELL_OPTIONS
+    return {name: conv(kw.pop(name, default)) for name, (default, conv) in DWELL_OPTIONS.items()}
 
 
 def _replica(p8, kw, seed):
@@ -232,10 +239,12 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
     `np.random.seed()` (spgg.py:98)."""
     import torch
     from .engine import BatchEngine, reference_init
-    from .spgg import _write_pngs, record_histories, record_run_kwargs, track_positions, write_datasets
+    from .spgg import (_write_pngs, dwell_histories, dwell_option_values, record_histories, record_run_kwargs,
+                       track_positions, write_datasets)
     from .algorithms import canonical_name
     kw = dict(RUNNER_MODEL, **model_overrides)
     records = record_run_kwargs(pop_record_options(kw))
+    dwell_every, dwell_fields = dwell_option_values(pop_dwell_options(kw))
     L, iters = int(kw["L"]), int(kw["iterations"])
     p8s = [unpack(p) for p in param_list]
     seeds = list(seeds) if seeds is not None else [None] * len(p8s)
@@ -258,16 +267,18 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
         eng = BatchEngine(L, max(iters, 1), reps, use_second_order=so, state_representation=state,
                           rng="mt19937", init=inits, algorithm=alg)
         try:
-            eng.run(snapshots=True, png=save_png, progress=progress, **records)
+            eng.run(snapshots=True, png=save_png, progress=progress, dwell_every=dwell_every, **records)
             hist = eng.histories()
             record_hists = record_histories(eng, records)
+            dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
             for k, i in enumerate(idx):
                 folder = get_folder_name(*p8s[i])
                 make_folders(folder)
                 _q, R, S = eng.final_state(k)
                 write_datasets(os.path.join(folder, "data", "experiment_data.h5"), hist[k], eng.snapshots[k],
                                S, R, kw["R_min"], kw["R_max"], track_positions(L),
-                               clusters=eng.cluster_sizes(k), **{arg: h and h[k] for arg, h in record_hists.items()})
+                               clusters=eng.cluster_sizes(k), dwell_hist=dwell_hist and dwell_hist[k],
+                               **{arg: h and h[k] for arg, h in record_hists.items()})
                 if save_png and eng.png_frames[k]:
                     _write_pngs(eng.png_frames[k], os.path.join(folder, "plots", "snapshots"))
                 coop = float(np.sum(S == 0)) / (L * L)

@@ -1,6 +1,6 @@
-"""What the device records cost (profiles/{clusters,correlations,reputation}/README.txt).
+"""What the device records cost (profiles/{clusters,correlations,reputation,dwell}/README.txt).
 
-    python tools/record_cost.py --record clusters|correlations|reputation [--repeats 5] [--iters 10000]
+    python tools/record_cost.py --record clusters|correlations|reputation|dwell [--repeats 5] [--iters 10000]
                                 [--legs LEG,LEG,...]
 
 Every variant runs in a fresh process (this driver never touches the GPU) and reports the median of
@@ -18,7 +18,14 @@ its repeats.  Legs (default: all of the record's, in this order):
                 pairs  the same for spgg_reputation_pairs, max_d as for correlations
                 host   both by the host path: copies of the S and R planes, np.histogram per strategy
                        and engine.host_reputation_pair_sums (np.roll)
-  every record  run    the whole cfg3 run (BatchEngine.run, MT19937, as bench.full_run times it) with
+  dwell         run    the whole run (BatchEngine.run, MT19937) of cfg3, cfg4 and cfg5 with dwell_every
+                       0 / 256 / 16, and the first 400 iterations alone (large eps: about half the agents
+                       flip per iteration); variant CONFIG:EVERY:ITERATIONS
+                launch device time per iteration of step(100) (HIP events on the current stream) without
+                       and with the dwell launch armed, in one process, after 20 and after 400
+                       iterations: the difference is the dwell launch's own cost; variant CONFIG:T
+                record device time of one spgg_dwell_record round / one spgg_dwell_fields round
+  every other   run    the whole cfg3 run (BatchEngine.run, MT19937, as bench.full_run times it) with
                        the record every {0, 16, 1} iterations (max_d = 100, 20 bins)
 """
 import argparse
@@ -209,13 +216,83 @@ def leg_run(a):
     return {"leg": "run", "variant": a.variant, "iterations": a.iters, **info, "seconds": out[1:]}
 
 
+def leg_dwell_run(a):
+    import torch
+    import bench
+    from spgg_amd.engine import BatchEngine
+    config, every, iters = a.variant.split(":")
+    _desc, L, M2, state, reps = bench.workload(config, 0)
+    out = []
+    for _ in range(a.repeats + 1):
+        eng = BatchEngine(L, int(iters), reps, use_second_order=M2, state_representation=state, rng="mt19937")
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.run(snapshots=False, dwell_every=int(every))
+            torch.cuda.synchronize()
+            out.append(time.perf_counter() - t0)
+            executed = eng.t - 1
+        finally:
+            eng.close()
+    return {"leg": "run", "variant": a.variant, "iterations": executed, "replicas": len(reps), "L": L,
+            "us_per_iter": [s / executed * 1e6 for s in out[1:]], "seconds": out[1:]}
+
+
+def leg_dwell_launch(a):
+    import torch
+    config, t = a.variant.split(":")
+    n_steps = 100
+    eng = _engine_at(config, int(t), int(t) + 2 * (a.repeats + 1) * n_steps + 1)
+    try:
+        cur = torch.cuda.current_stream(eng.dev)
+
+        def timed():
+            out = []
+            for _ in range(a.repeats + 1):   # (the first repeat warms up)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(cur)
+                eng.step(n_steps)   # (ordered: the groups' streams start after e0 and e1 waits for them)
+                e1.record(cur)
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1) * 1e3 / n_steps)
+            return out[1:]
+        off = timed()
+        eng.dwell_start()
+        on = timed()
+        flips = eng.dwell_record()[:, 5].sum() / (eng.R * eng.n * (a.repeats + 1) * n_steps)
+        return {"leg": "launch", "variant": a.variant, "replicas": eng.R, "L": eng.L, "groups": eng.G,
+                "flip_share": float(flips), "us_per_iter_off": off, "us_per_iter_on": on}
+    finally:
+        eng.close()
+
+
+def leg_dwell_record(a):
+    import torch
+    config, what = a.variant.split(":")
+    eng = _engine_at(config, 200, 300)
+    try:
+        eng.dwell_start()
+        eng.step(20)
+        torch.cuda.synchronize()
+        fn, width, dtype = ((eng.lib.spgg_dwell_record, 61, torch.int64) if what == "record" else
+                            (eng.lib.spgg_dwell_fields, 3 * eng.n, torch.int32))
+        out_buf = torch.zeros((eng.R, width), dtype=dtype, device=eng.dev)
+        us = _timed_rounds(eng, a, lambda g, s: fn(g["ctx"], eng.t, out_buf[g["r0"]].data_ptr(), width, s))
+        return {"leg": "record", "variant": a.variant, "replicas": eng.R, "L": eng.L, "us_per_round": us}
+    finally:
+        eng.close()
+
+
 RUN = (leg_run, ["0", "16", "1"])
 LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
                      "call": (leg_call, [f"{c}:{s}:{p}" for c in ("cfg3", "cfg4") for s in ("record", "sizes")
                                          for p in (0, 1)]),
                      "run": (leg_run, ["0", "1", "16"])},
         "correlations": {"call": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN},
-        "reputation": {"hist": (leg_call, SHAPES), "pairs": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN}}
+        "reputation": {"hist": (leg_call, SHAPES), "pairs": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN},
+        "dwell": {"run": (leg_dwell_run, [f"{c}:{e}:{i}" for c in SHAPES for i in ("iters", "400") for e in (0, 256, 16)]),
+                  "launch": (leg_dwell_launch, [f"{c}:{t}" for c in SHAPES for t in (20, 400)]),
+                  "record": (leg_dwell_record, [f"{c}:{w}" for c in SHAPES for w in ("record", "fields")])}}
 
 
 def main():
@@ -231,9 +308,10 @@ def main():
     if a.child:
         print("RESULT " + json.dumps(legs[a.child][0](a)), flush=True)
         return 0
-    width = 16 if a.record == "clusters" else 6
+    width = 16 if a.record in ("clusters", "dwell") else 6
     for leg in (a.legs.split(",") if a.legs else legs):
         for variant in legs[leg][1]:
+            variant = variant.replace(":iters", f":{a.iters}")
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--record", a.record, "--child", leg,
                                 "--variant", variant, "--repeats", str(a.repeats), "--iters", str(a.iters)],
                                capture_output=True, text=True, timeout=600)
@@ -242,14 +320,16 @@ def main():
                 print(f"{leg} {variant}: failed rc={r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", flush=True)
                 return 1   # nothing more is started after a failed leg
             d = json.loads(line[0][7:])
-            for key, unit in (("us_per_round", "us"), ("hist_seconds", "s (hist)"), ("seconds", "s")):
+            for key, unit in (("us_per_round", "us"), ("us_per_iter", "us/iter"), ("us_per_iter_off", "us/iter (off)"),
+                              ("us_per_iter_on", "us/iter (armed)"), ("hist_seconds", "s (hist)"), ("seconds", "s")):
                 vals = d.get(key)
                 if not vals:
                     continue
                 print(f"{leg:5s} {variant:{width}s} median {statistics.median(vals):.6g} {unit}  "
                       f"min {min(vals):.6g} max {max(vals):.6g}  n={len(vals)}  "
                       + " ".join(f"{k}={v}" for k, v in d.items()
-                                 if k not in ("seconds", "hist_seconds", "us_per_round", "leg", "variant")),
+                                 if k not in ("seconds", "hist_seconds", "us_per_round", "us_per_iter", "us_per_iter_off",
+                                              "us_per_iter_on", "leg", "variant")),
                       flush=True)
     return 0
 
