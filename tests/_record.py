@@ -73,12 +73,14 @@ class Record:
 
 
 def oracle_params(params, L, T, M2, state, algorithm):
-    """O.Params from an O.Params, a dict of PARAM_KEYS or an object with those attributes."""
+    """O.Params from an O.Params, a dict of PARAM_KEYS or an object with those attributes; the
+    operator's own alg_alpha / alg_gamma are carried over where the dict or object has them."""
     over = dict(L=L, iterations=T, use_second_order=M2, state_representation=state, algorithm=algorithm)
     if isinstance(params, O.Params):
         return dataclasses.replace(params, **over)
-    kw = dict(params) if isinstance(params, dict) else {k: getattr(params, k) for k in PARAM_KEYS}
-    return O.Params(**{k: v for k, v in kw.items() if k in PARAM_KEYS}, **over)
+    keys = PARAM_KEYS + ("alg_alpha", "alg_gamma")
+    kw = dict(params) if isinstance(params, dict) else {k: getattr(params, k) for k in keys if hasattr(params, k)}
+    return O.Params(**{k: v for k, v in kw.items() if k in keys}, **over)
 
 
 def _rep_unit(p):

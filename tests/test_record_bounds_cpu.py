@@ -17,6 +17,7 @@ import pytest
 
 from oracle import spgg_oracle as O
 from spgg_amd.engine import epsilon_table, histories_from_stats
+from tests import _params as P
 from tests import _record as R
 from tests._golden import Case, case_names
 
@@ -60,12 +61,23 @@ VARIANTS[120].append(("expected_sarsa", False, 0.3))
 CASES = [(L, alg, M2, gain) for L in sorted(VARIANTS) for alg, M2, gain in VARIANTS[L]]
 TILES = dict(R.GPU_LATTICES)
 TILES[200] = (40, 25, 4, 1)
+# The rows the parameter-space tests step (tests/_params.py: all but the payoff-only ones) at L = 18;
+# the last element of a case is then the row's name.
+ROWS = {k: v for k, v in P.all_rows().items() if not k.startswith("a-")}
+ROW_CASES = [(18, "qlearning", True, name) for name in sorted(ROWS)]
+ROW_CASES += [(18, "double_qlearning", True, name) for name in sorted(ROWS) if name.startswith("b-dyadic")]
+ALL_CASES = CASES + ROW_CASES
 
 
 @functools.lru_cache(maxsize=None)
 def _rec(L, alg, M2, gain):
     T = 3 if L >= 200 else T_CPU
-    return R.philox_record(L, T, dict(R.BASE, rep_gain_C=gain, r=3.4), 5, 0, M2, "reputation", alg, keep_terms=True)
+    params = ROWS[gain] if isinstance(gain, str) else dict(R.BASE, rep_gain_C=gain, r=3.4)
+    return R.philox_record(L, T, params, 5, 0, M2, "reputation", alg, keep_terms=True)
+
+
+def _dyadic(gain):
+    return P.unit_of(ROWS[gain]) is not None if isinstance(gain, str) else gain == 1.0
 
 
 def _steps(rec):
@@ -139,10 +151,10 @@ def model_ratio(rec, t, tile, rng, ulps):
     return fold(tile_totals(term, tile) * 100.0, tile[3], rng)
 
 
-@pytest.mark.parametrize("L,alg,M2,gain", CASES)
+@pytest.mark.parametrize("L,alg,M2,gain", ALL_CASES)
 def test_reference_in_device_order_stays_inside_f64_bounds(L, alg, M2, gain):
     rec = _rec(L, alg, M2, gain)
-    assert rec.rep_dyadic == (gain == 1.0)
+    assert rec.rep_dyadic == _dyadic(gain)
     b = R.bounds(rec)
     rng = np.random.RandomState(L)
     for t in _steps(rec):
@@ -196,7 +208,7 @@ def _check_finalize(rec, rew_c_of):
         assert got[R.SUM_WRR] == v[t, R.SUM_WRR] and got[R.SW_DC] == v[t, R.SW_DC]
 
 
-@pytest.mark.parametrize("L,alg,M2,gain", CASES)
+@pytest.mark.parametrize("L,alg,M2,gain", ALL_CASES)
 def test_regrouped_slots_stay_inside_bounds(L, alg, M2, gain):
     rec = _rec(L, alg, M2, gain)
     rng = np.random.RandomState(L + 1)
@@ -231,13 +243,16 @@ def model_pct(rec, t, tile, rng, ulps):
     return fold(tile_totals(term, tile, f32_threads=True) * 100.0, tile[3], rng)
 
 
-@pytest.mark.parametrize("L,alg,M2,gain", CASES)
+@pytest.mark.parametrize("L,alg,M2,gain", ALL_CASES)
 def test_reference_in_f32_chain_stays_inside_pct_bound(L, alg, M2, gain):
     rec = _rec(L, alg, M2, gain)
     b = R.bounds(rec)
     rng = np.random.RandomState(L + 2)
     for t in _steps(rec):
-        assert rec.mag[t, R.SUM_PCT] > 0
+        if rec.params.influence_factor == 0.0:      # nu = +0: the slot and its bound are exactly 0
+            assert rec.value[t, R.SUM_PCT] == 0.0 and b[t, R.SUM_PCT] == 0.0
+        else:
+            assert rec.mag[t, R.SUM_PCT] > 0
         for ulps in (-1, 0, 1):
             v = model_pct(rec, t, TILES[L], rng, ulps)
             assert abs(v - rec.value[t, R.SUM_PCT]) <= b[t, R.SUM_PCT], (t, ulps, v, rec.value[t, R.SUM_PCT])
@@ -261,7 +276,7 @@ def _median_term(rec, t, k):
     return float(np.median(x)) if x.size else None
 
 
-@pytest.mark.parametrize("L,alg,M2,gain", CASES)
+@pytest.mark.parametrize("L,alg,M2,gain", ALL_CASES)
 def test_one_agent_moves_a_sum_by_far_more_than_its_bound(L, alg, M2, gain):
     """Dropping or repeating one agent's median-magnitude non-zero term moves every f64 float slot
     by more than 100 x its bound (a loss is sure to be seen from 2 x on: the honest error is within
@@ -276,6 +291,13 @@ def test_one_agent_moves_a_sum_by_far_more_than_its_bound(L, alg, M2, gain):
     rec = _rec(L, alg, M2, gain)
     b = R.bounds(rec)
     slots = [k for k in R.F64_SUM_SLOTS + R.REGROUPED if not (k == R.SUMR and rec.rep_dyadic)]
+    # slots whose every term the parameters make exactly 0 (their bounds are 0 too: bit-equal on the
+    # device): no reputation reward at w_P = 1; 0 * P and a defector's reward 0 * P + w_rep * 0 at w_P = 0
+    if rec.params.reward_weight_rep == 0.0:
+        slots.remove(R.SUM_RATIO_C)
+    if rec.params.reward_weight_payoff == 0.0:
+        slots = [k for k in slots if k not in (R.SUM_WPP, R.SUM_REW_D)]
+        assert not b[:, R.SUM_WPP].any()
     seen = set()
     for t in _steps(rec):
         for k in slots:
@@ -297,7 +319,9 @@ def test_one_agent_moves_a_sum_by_far_more_than_its_bound(L, alg, M2, gain):
                     continue
             assert med > 100 * b[t, k], (t, R.SLOT_NAMES[k], med, b[t, k])
         med = _median_term(rec, t, R.SUM_PCT)
-        if L <= 200:
+        if rec.params.influence_factor == 0.0:
+            assert med is None and b[t, R.SUM_PCT] == 0.0
+        elif L <= 200:
             assert med > 2 * b[t, R.SUM_PCT], (t, med, b[t, R.SUM_PCT])
         else:
             assert med < 2 * b[t, R.SUM_PCT] and med < 100 * b[t, R.SUM_PCT], (t, med, b[t, R.SUM_PCT])
