@@ -17,6 +17,8 @@ ABI_VERSION = 19
 OK, E_ARG, E_STATE, E_HIP = 0, -1, -2, -3
 GEN_ERR_SPIN = 1
 CLUSTERS_MAX_PASSES = 32   # SPGG_CLUSTERS_MAX_PASSES (spgg_abi.h): pass cap of spgg_clusters
+CLUSTERS_TILED_MAX_RETRIES = 256   # SPGG_CLUSTERS_TILED_MAX_RETRIES: retry cap of one seam union of spgg_clusters_tiled
+CLUSTERS_TILE_MIN, CLUSTERS_TILE_MAX, CLUSTERS_TILE_DEFAULT = 8, 200, 64   # tile sides of spgg_clusters_tiled (0: the default)
 STATE_REPUTATION, STATE_ACTION = 0, 1
 RNG_INJECT, RNG_MT19937, RNG_PHILOX = 0, 1, 2
 RNG_MODES = {"inject": RNG_INJECT, "mt19937": RNG_MT19937, "philox": RNG_PHILOX}
@@ -46,7 +48,7 @@ EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create
             "spgg_status", "spgg_persistent", "spgg_clusters", "spgg_clusters_max_side",
             "spgg_correlations", "spgg_correlations_max_side", "spgg_reputation_hist",
             "spgg_reputation_pairs", "spgg_reputation_max_side", "spgg_dwell_bind", "spgg_dwell_reset",
-            "spgg_dwell_record", "spgg_dwell_fields")
+            "spgg_dwell_record", "spgg_dwell_fields", "spgg_clusters_tiled", "spgg_clusters_tiled_workspace")
 # test-only entry points (include/spgg_test.h): exported by the library, not part of the product ABI
 TEST_EXPORTED = ("spgg_test_set_error",)
 
@@ -130,6 +132,10 @@ def load(path: str | None = None):
         lib.spgg_clusters.argtypes = [vp, i32, i32, vp, vp, ctypes.c_int64, vp]
         lib.spgg_clusters_max_side.restype = ctypes.c_int
         lib.spgg_clusters_max_side.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.spgg_clusters_tiled.restype = ctypes.c_int
+        lib.spgg_clusters_tiled.argtypes = [vp, i32, i32, i32, vp, vp, vp, ctypes.c_int64, vp]
+        lib.spgg_clusters_tiled_workspace.restype = ctypes.c_int
+        lib.spgg_clusters_tiled_workspace.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
         lib.spgg_correlations.restype = ctypes.c_int
         lib.spgg_correlations.argtypes = [vp, i32, i32, vp, ctypes.c_int64, vp]
         lib.spgg_correlations_max_side.restype = ctypes.c_int

@@ -18,7 +18,8 @@ SRC = [os.path.join(PKG_DIR, "csrc", "spgg_kernels.hip"),
        os.path.join(PKG_DIR, "csrc", "spgg_clusters.hip"),   # cluster labelling (its own object)
        os.path.join(PKG_DIR, "csrc", "spgg_correlations.hip"),   # pair counts (its own object)
        os.path.join(PKG_DIR, "csrc", "spgg_reputation.hip"),   # reputation record (its own object)
-       os.path.join(PKG_DIR, "csrc", "spgg_dwell.hip")]   # strategy dwell record (its own object)
+       os.path.join(PKG_DIR, "csrc", "spgg_dwell.hip"),   # strategy dwell record (its own object)
+       os.path.join(PKG_DIR, "csrc", "spgg_clusters_tiled.hip")]   # cluster labelling over many workgroups (its own object)
 INC = os.path.join(ROOT, "include")
 OUT = os.path.join(PKG_DIR, "libspgg_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -36,7 +37,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 DEPS = SRC + [os.path.join(INC, "spgg_abi.h"), os.path.join(INC, "spgg_test.h"), os.path.join(PKG_DIR, "csrc", "spgg_device.h"),
               os.path.join(PKG_DIR, "csrc", "spgg_mt.h"), os.path.join(PKG_DIR, "csrc", "spgg_clusters.h"),
               os.path.join(PKG_DIR, "csrc", "spgg_correlations.h"), os.path.join(PKG_DIR, "csrc", "spgg_reputation.h"),
-              os.path.join(PKG_DIR, "csrc", "spgg_dwell.h")]
+              os.path.join(PKG_DIR, "csrc", "spgg_dwell.h"), os.path.join(PKG_DIR, "csrc", "spgg_clusters_tiled.h")]
 
 
 def build_id(defines=()):
@@ -73,7 +74,7 @@ def build(force=False, verbose=True, out=OUT, defines=()):
     with tempfile.TemporaryDirectory() as tmp:
         objs = [os.path.join(tmp, f"tu{k}.o") for k in TUS] + [os.path.join(tmp, "mt.o"), os.path.join(tmp, "clusters.o"),
                                                                  os.path.join(tmp, "correlations.o"), os.path.join(tmp, "reputation.o"),
-                                                                 os.path.join(tmp, "dwell.o")]
+                                                                 os.path.join(tmp, "dwell.o"), os.path.join(tmp, "clusters_tiled.o")]
         cmds = [[HIPCC, *FLAGS, *extra, f"-DSPGG_TU={k}", f"-I{INC}", "-c", SRC[0], "-o", o]
                 for k, o in zip(TUS, objs)]
         for src, o in zip(SRC[1:], objs[len(TUS):]):

@@ -45,6 +45,7 @@
 #include "spgg_device.h"
 #include "spgg_mt.h"
 #include "spgg_clusters.h"
+#include "spgg_clusters_tiled.h"
 #include "spgg_correlations.h"
 #include "spgg_reputation.h"
 #include "spgg_dwell.h"
@@ -3681,6 +3682,25 @@ int spgg_clusters(spgg_ctx* c, int32_t t, int32_t periodic, int32_t* sizes, int3
   spgg_cl::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, periodic, sizes, rec,
                         rec_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_clusters launch");
+}
+
+int spgg_clusters_tiled_workspace(const spgg_ctx* c, int64_t* words_per_rep) {
+  if (!c || !words_per_rep) return SPGG_E_ARG;
+  *words_per_rep = spgg_clt::workspace_words((int64_t)c->cfg.L * c->cfg.L);
+  return SPGG_OK;
+}
+
+int spgg_clusters_tiled(spgg_ctx* c, int32_t t, int32_t periodic, int32_t tile, int32_t* work, int32_t* sizes,
+                        int32_t* rec, int64_t rec_stride, void* stream) {
+  if (const int rc = observable_check(c, "spgg_clusters_tiled", rec && work, false, t)) return rc;
+  if (tile == 0) tile = spgg_clt::kDefaultTile;
+  if (tile < spgg_clt::kMinTile || tile > spgg_clt::kMaxTile)
+    return fail(c, SPGG_E_ARG, "spgg_clusters_tiled: tile = " + std::to_string(tile) + " outside " +
+                                   std::to_string(spgg_clt::kMinTile) + " .. " + std::to_string(spgg_clt::kMaxTile) +
+                                   " (0: the library's choice)");
+  spgg_clt::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, periodic, tile, work, sizes,
+                   rec, rec_stride, reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_clusters_tiled launch");
 }
 
 int spgg_correlations_max_side(const spgg_ctx* c, int32_t* side) {

@@ -33,7 +33,7 @@ import torch
 from . import _lib as C
 from .algorithms import canonical_name
 from .dwell import DWELL_SLOTS, Dwell
-from .records import (KINDS, next_boundary,  # noqa: F401  (the host models stay importable from here)
+from .records import (KINDS, next_boundary, clusters_cap_text,  # noqa: F401  (the host models stay importable from here)
                       host_cluster_sizes, host_pair_counts, correlation_function, correlation_length,
                       reputation_bin_edges, host_reputation_pair_sums, reputation_correlation_function)
 
@@ -332,6 +332,7 @@ class BatchEngine:
         self.records = {}          # name (records.KINDS, "dwell") -> the in-run Record of the last run that asked for it
         self._final_cache = {}     # final-state observables (cluster_sizes, pair_counts, ...) until the next step
         self.dwell_t_ref = None    # the reference iteration of the strategy dwell record while it is tracked
+        self._clusters_work = None   # the workspace of spgg_clusters_tiled, allocated on first use
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -700,7 +701,8 @@ class BatchEngine:
             progress: Optional[Callable[[int], None]] = None, clusters_every: int = 0,
             clusters_periodic: bool = False, correlations_every: int = 0,
             correlations_max_d: Optional[int] = None, reputation_every: int = 0,
-            reputation_bins: int = 20, reputation_max_d: Optional[int] = None, dwell_every: int = 0):
+            reputation_bins: int = 20, reputation_max_d: Optional[int] = None, dwell_every: int = 0,
+            clusters_tiled=False):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -718,7 +720,10 @@ class BatchEngine:
         record, changed settings start a new one at the current t; every setting is checked
         (ValueError) before anything is allocated or enqueued; with 0 nothing else is enqueued.
           clusters_every: spgg_clusters of S_t (number of cooperator clusters, largest cluster, C-D
-            bonds; clusters_periodic: wrapped lattice); read with cluster_histories().
+            bonds; clusters_periodic: wrapped lattice); read with cluster_histories().  clusters_tiled:
+            False: the one-workgroup LDS kernel, lattices up to clusters_max_side; True: spgg_clusters_tiled
+            (one replica over many workgroups, any side) with the library's tile; an int: with that tile
+            side (8 .. 200).  Same record either way; part of the record's settings.
           correlations_every: spgg_correlations of S_t, the cooperator pair counts at the distances
             0 .. correlations_max_d (None: L // 2); read with correlation_histories().
           reputation_every: spgg_reputation_hist of (S_t, R_t), the joint histogram strategy x bin
@@ -732,7 +737,7 @@ class BatchEngine:
         same schedule; read with dwell_histories().  A run continued with the same k keeps its record
         and its reference, another k starts afresh at the current t, 0 stops the tracking of an
         earlier run and drops its record; not on an engine that steps in persistent launches."""
-        asked = {"clusters": (clusters_every, clusters_periodic), "correlations": (correlations_every, correlations_max_d),
+        asked = {"clusters": (clusters_every, clusters_periodic, clusters_tiled), "correlations": (correlations_every, correlations_max_d),
                  "reputation": (reputation_every, reputation_bins, reputation_max_d)}
         keys = {name: KINDS[name].validate(self, *a) for name, a in asked.items()}   # (before any allocation)
         dwell_every = int(dwell_every)
@@ -901,21 +906,33 @@ class BatchEngine:
         label order (ascending smallest raster index: scipy.ndimage.label's, spgg.py:631-633);
         shape (0,) without a cooperator.  periodic=False: the lattice edge is a wall (the
         reference's dataset); True: it wraps, as the dynamics do.  Labelled on the device, all
-        replicas at once (one spgg_clusters launch per replica group) and cached until the engine
-        steps again; lattices above the supported side are labelled on the host, same result."""
+        replicas at once (one spgg_clusters call per replica group) and cached until the engine
+        steps again; lattices above spgg_clusters' side (clusters_max_side) are labelled by
+        spgg_clusters_tiled over many workgroups, same result."""
         periodic = bool(periodic)
-        if self.L > self.clusters_max_side:
-            return host_cluster_sizes(self.final_state(k)[2], periodic)
         if ("sizes", periodic) not in self._final_cache:
             sizes = torch.empty((self.R, self.n), dtype=torch.int32, device=self.dev)
-            count = self._final(("cluster_record", periodic), self.lib.spgg_clusters, (int(periodic), sizes), 3)[:, 0]
+            tiled = self.L > self.clusters_max_side   # above the LDS kernel's side: spgg_clusters_tiled, the library's tile
+            fn, args = ((self.lib.spgg_clusters_tiled, (int(periodic), 0, self._clusters_workspace(), sizes)) if tiled
+                        else (self.lib.spgg_clusters, (int(periodic), sizes)))
+            count = self._final(("cluster_record", periodic), fn, args, 3)[:, 0]
             flat = sizes.view(-1)
             vals = flat[flat > 0].cpu().numpy().astype(np.int64)   # compacted on the device
             if np.any(count < 0):
-                raise C.SpggError(f"spgg_clusters: replicas {np.nonzero(count < 0)[0].tolist()} ran into the "
-                                  f"labelling's pass cap ({C.CLUSTERS_MAX_PASSES})")
+                raise C.SpggError(f"{fn.__name__}: replicas {np.nonzero(count < 0)[0].tolist()} ran into "
+                                  + clusters_cap_text(tiled))
             self._final_cache["sizes", periodic] = np.split(vals, np.cumsum(count)[:-1])
         return self._final_cache["sizes", periodic][k]
+
+    def _clusters_workspace(self):
+        """The (R, words) int32 workspace of spgg_clusters_tiled (parent and count planes, 8 B per agent, plus the
+        flag words), allocated on first use; _observe hands each replica group its replica slice."""
+        if self._clusters_work is None:
+            words = ctypes.c_int64(0)
+            C.check(self.lib.spgg_clusters_tiled_workspace(self.ctx, ctypes.byref(words)), self.ctx,
+                    "spgg_clusters_tiled_workspace")
+            self._clusters_work = torch.empty((self.R, int(words.value)), dtype=torch.int32, device=self.dev)
+        return self._clusters_work
 
     def cluster_histories(self):
         """Per replica, the in-run cluster record of run(clusters_every=k): cluster_history_iters

@@ -62,24 +62,55 @@ class Record:
         return [self.datasets(eng, k, its[k], *[h[k, :len(its[k])] for h in host]) for k in range(eng.R)]
 
 
+def clusters_tile(tiled):
+    """The tile side a clusters_tiled value asks for: False -> None (the one-workgroup LDS kernel),
+    True -> 0 (the library's tile), an int -> that side, 8 .. 200."""
+    if tiled is False or tiled is None:
+        return None
+    if tiled is True:
+        return 0
+    tile = int(tiled)
+    if not C.CLUSTERS_TILE_MIN <= tile <= C.CLUSTERS_TILE_MAX:
+        raise ValueError(f"clusters_tiled: a tile side in {C.CLUSTERS_TILE_MIN} .. {C.CLUSTERS_TILE_MAX} "
+                         f"(or True for the library's, {C.CLUSTERS_TILE_DEFAULT}), got {tiled!r}")
+    return tile
+
+
+def clusters_cap_text(tiled) -> str:
+    """What a cluster count of -1 means, by the path that wrote it."""
+    if not tiled:
+        return f"the labelling's pass cap ({C.CLUSTERS_MAX_PASSES})"
+    return (f"a cap of the tiled labelling (a tile's pass cap {C.CLUSTERS_MAX_PASSES}, a root walk of n steps or "
+            f"a seam union's retry cap {C.CLUSTERS_TILED_MAX_RETRIES})")
+
+
 class Clusters(Record):
-    """spgg_clusters of S_t: (clusters, largest cluster, C-D bonds) int32; key (every, periodic)."""
+    """spgg_clusters of S_t: (clusters, largest cluster, C-D bonds) int32; key (every, periodic, tile): tile
+    None for the one-workgroup LDS kernel, else the tile side of spgg_clusters_tiled (0: the library's)."""
 
     @staticmethod
-    def validate(eng, every, periodic):
+    def validate(eng, every, periodic, tiled=False):
         every = _every("clusters_every", every)
-        if every and eng.L > eng.clusters_max_side:
-            raise ValueError(f"clusters_every: the device labels lattices up to side {eng.clusters_max_side}, "
-                             f"L = {eng.L} (label snapshots on the host: engine.host_cluster_sizes)")
-        return every, bool(periodic)
+        tile = clusters_tile(tiled)
+        if tile is not None and not every:
+            raise ValueError("clusters_tiled needs clusters_every > 0 (nothing is recorded otherwise)")
+        if every and tile is None and eng.L > eng.clusters_max_side:
+            raise ValueError(f"clusters_every: the one-workgroup kernel labels lattices up to side {eng.clusters_max_side}, "
+                             f"L = {eng.L} (clusters_tiled=True records any side; or label snapshots on the host: "
+                             "engine.host_cluster_sizes)")
+        return every, bool(periodic), tile
 
     def calls(self, eng):
-        return [(eng.lib.spgg_clusters, (int(self.key[1]), None), 3, "int32")]
+        _, periodic, tile = self.key
+        if tile is None:
+            return [(eng.lib.spgg_clusters, (int(periodic), None), 3, "int32")]
+        return [(eng.lib.spgg_clusters_tiled, (int(periodic), tile, eng._clusters_workspace(), None), 3, "int32")]
 
     def datasets(self, eng, k, its, r):
         if np.any(r[:, 0] < 0):
-            raise C.SpggError(f"spgg_clusters: replica {k} ran into the labelling's pass cap "
-                              f"({C.CLUSTERS_MAX_PASSES}) at iterations {its[r[:, 0] < 0].tolist()}")
+            tiled = self.key[2] is not None
+            raise C.SpggError(f"{'spgg_clusters_tiled' if tiled else 'spgg_clusters'}: replica {k} ran into "
+                              f"{clusters_cap_text(tiled)} at iterations {its[r[:, 0] < 0].tolist()}")
         return dict(cluster_history_iters=its, cluster_count_history=r[:, 0].copy(),
                     largest_cluster_history=r[:, 1].copy(), cd_bond_history=r[:, 2].copy())
 

@@ -66,6 +66,25 @@ DWELL_OPTIONS = {
 }
 
 
+def _tiled(v):
+    return v if isinstance(v, bool) else (int(v) if v else False)
+
+
+# The tiled cluster labelling's option, a class attribute of SPGG like the others in a table of its
+# own.  name -> (default, BatchEngine.run keyword argument, conversion).  cluster_history_tiled: False:
+# the in-run cluster record is written by the one-workgroup kernel (lattices up to side 200); True: by
+# spgg_clusters_tiled (any side) with the library's tile; an int: with that tile side (8 .. 200).  Needs
+# cluster_history_every > 0; the datasets are the same.
+CLUSTER_TILED_OPTIONS = {
+    "cluster_history_tiled": (False, "clusters_tiled", _tiled),
+}
+
+
+def cluster_tiled_run_kwargs(values):
+    """BatchEngine.run's clusters_tiled keyword argument from option values (a mapping; absent: default)."""
+    return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in CLUSTER_TILED_OPTIONS.items()}
+
+
 def dwell_option_values(values):
     """(dwell_every, dwell_fields) from option values (a mapping; absent: default)."""
     every, fields = (conv(values.get(name, default)) for name, (default, conv) in DWELL_OPTIONS.items())
@@ -97,7 +116,8 @@ class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
-    # (the RECORD_OPTIONS and DWELL_OPTIONS are class attributes too, set at their defaults below the class)
+    # (the RECORD_OPTIONS, DWELL_OPTIONS and CLUSTER_TILED_OPTIONS are class attributes too, set at their defaults
+    # below the class)
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -206,9 +226,10 @@ class SPGG:
         try:
             records = record_run_kwargs({name: getattr(self, name) for name in RECORD_OPTIONS})
             dwell_every, dwell_fields = dwell_option_values({name: getattr(self, name) for name in DWELL_OPTIONS})
-            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records)
+            tiled = cluster_tiled_run_kwargs({name: getattr(self, name) for name in CLUSTER_TILED_OPTIONS})
+            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records, **tiled)
             hist = eng.histories()[0]
-            clusters = eng.cluster_sizes(0)   # labelled on the device (host above its supported side)
+            clusters = eng.cluster_sizes(0)   # labelled on the device (over many workgroups above side 200)
             record_hists = {arg: h and h[0] for arg, h in record_histories(eng, records).items()}
             dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
             Q, R, S = eng.final_state(0)
@@ -251,6 +272,8 @@ class SPGG:
 for _name, (_default, _kw, _conv) in RECORD_OPTIONS.items():
     setattr(SPGG, _name, _default)
 for _name, (_default, _conv) in DWELL_OPTIONS.items():
+    setattr(SPGG, _name, _default)
+for _name, (_default, _kw, _conv) in CLUSTER_TILED_OPTIONS.items():
     setattr(SPGG, _name, _default)
 
 

@@ -188,7 +188,7 @@ def run_one_experiment(params: Tuple, **model_overrides) -> Tuple[Tuple, Tuple[f
     folder = get_folder_name(*p8)
     make_folders(folder)
     kw = dict(RUNNER_MODEL, **model_overrides)
-    records = dict(pop_record_options(kw), **pop_dwell_options(kw))
+    records = dict(pop_record_options(kw), **pop_dwell_options(kw), **pop_cluster_tiled_options(kw))
     spgg = SPGG(r=r, alpha=alpha, influence_factor=kappa, use_second_order=so,
                 reward_weight_payoff=w_p, rep_gain_C=gain, state_representation=state,
                 algorithm=algorithm, **kw)
@@ -216,6 +216,13 @@ def pop_dwell_options(kw):
     return {name: conv(kw.pop(name, default)) for name, (default, conv) in DWELL_OPTIONS.items()}
 
 
+def pop_cluster_tiled_options(kw):
+    """Take the tiled cluster labelling's option (spgg.CLUSTER_TILED_OPTIONS) out of the model
+    overrides kw the same way."""
+    from .spgg import CLUSTER_TILED_OPTIONS
+    return {name: conv(kw.pop(name, default)) for name, (default, _run_kw, conv) in CLUSTER_TILED_OPTIONS.items()}
+
+
 def _replica(p8, kw, seed):
     from .engine import ReplicaParams
     r, kappa, _so, alpha, w_p, gain, _state, _alg = p8
@@ -239,12 +246,13 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
     `np.random.seed()` (spgg.py:98)."""
     import torch
     from .engine import BatchEngine, reference_init
-    from .spgg import (_write_pngs, dwell_histories, dwell_option_values, record_histories, record_run_kwargs,
+    from .spgg import (_write_pngs, cluster_tiled_run_kwargs, dwell_histories, dwell_option_values, record_histories, record_run_kwargs,
                        track_positions, write_datasets)
     from .algorithms import canonical_name
     kw = dict(RUNNER_MODEL, **model_overrides)
     records = record_run_kwargs(pop_record_options(kw))
     dwell_every, dwell_fields = dwell_option_values(pop_dwell_options(kw))
+    tiled = cluster_tiled_run_kwargs(pop_cluster_tiled_options(kw))
     L, iters = int(kw["L"]), int(kw["iterations"])
     p8s = [unpack(p) for p in param_list]
     seeds = list(seeds) if seeds is not None else [None] * len(p8s)
@@ -267,7 +275,7 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
         eng = BatchEngine(L, max(iters, 1), reps, use_second_order=so, state_representation=state,
                           rng="mt19937", init=inits, algorithm=alg)
         try:
-            eng.run(snapshots=True, png=save_png, progress=progress, dwell_every=dwell_every, **records)
+            eng.run(snapshots=True, png=save_png, progress=progress, dwell_every=dwell_every, **records, **tiled)
             hist = eng.histories()
             record_hists = record_histories(eng, records)
             dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)

@@ -11,6 +11,13 @@ its repeats.  Legs (default: all of the record's, in this order):
                 call   device time of one spgg_clusters round over every replica (HIP events over 100
                        rounds) at cfg3's and cfg4's shapes: record only / with the size planes,
                        walls / periodic
+                tiled  the same for one spgg_clusters_tiled round (five launches): variant
+                       CONFIG:TILE:record|sizes, TILE a tile side, 0 for the library's or "lds" for the
+                       one-workgroup spgg_clusters in the same session (cfg3 / cfg4 only); cfg5 sweeps the
+                       tile sides that settle the library's
+                host5  the host path cfg5 (1 x L=1000) had before: copy of S + scipy label + bincount
+                run5   the whole cfg5 run (BatchEngine.run, MT19937) with clusters_every 0 / 256 / 16,
+                       clusters_tiled=True
   correlations  call   the same for spgg_correlations at cfg3's, cfg4's (max_d = 100) and cfg5's
                        (max_d = 500) shapes
                 host   the same counts by engine.host_pair_counts on host copies of the planes
@@ -147,6 +154,75 @@ def leg_call(a):
         return {"leg": a.child, "variant": a.variant, **info, "replicas": eng.R, "groups": eng.G, "us_per_round": us}
     finally:
         eng.close()
+
+
+def leg_tiled(a):
+    import ctypes
+    import torch
+    config, tile, sizes = a.variant.split(":")
+    eng = _engine_at(config, 500, 600)
+    try:
+        out_buf = torch.zeros((eng.R, 3), dtype=torch.int32, device=eng.dev)
+        planes = torch.zeros((eng.R, eng.n), dtype=torch.int32, device=eng.dev) if sizes == "sizes" else None
+
+        def plane_ptr(g):
+            return planes[g["r0"]].data_ptr() if planes is not None else None
+        if tile == "lds":
+            us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_clusters(
+                g["ctx"], eng.t, 0, plane_ptr(g), out_buf[g["r0"]].data_ptr(), 3, s))
+        else:
+            words = ctypes.c_int64(0)
+            assert eng.lib.spgg_clusters_tiled_workspace(eng.ctx, ctypes.byref(words)) == 0
+            work = torch.empty((eng.R, words.value), dtype=torch.int32, device=eng.dev)
+            us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_clusters_tiled(
+                g["ctx"], eng.t, 0, int(tile), work[g["r0"]].data_ptr(), plane_ptr(g), out_buf[g["r0"]].data_ptr(), 3, s))
+        rec = out_buf.cpu().numpy()
+        assert (rec[:, 0] >= 0).all(), rec   # no cap
+        return {"leg": "tiled", "variant": a.variant, "L": eng.L, "replicas": eng.R, "groups": eng.G,
+                "clusters": int(rec[:, 0].sum()), "largest": int(rec[:, 1].max()), "us_per_round": us}
+    finally:
+        eng.close()
+
+
+def leg_host5(a):
+    import torch
+    from spgg_amd import spgg
+    eng = _engine_at(a.variant, 500, 600)
+    try:
+        device = sum(len(eng.cluster_sizes(k)) for k in range(eng.R))   # (above side 200: the tiled path)
+        out = []
+        for _ in range(a.repeats + 1):   # (the first repeat warms up: the scipy import)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = sum(len(spgg.cluster_sizes(S & 1)) for S in _final_planes(eng, eng.S))
+            out.append(time.perf_counter() - t0)
+        return {"leg": "host5", "variant": a.variant, "L": eng.L, "replicas": eng.R, "clusters": n,
+                "equals_device": n == device, "seconds": out[1:]}
+    finally:
+        eng.close()
+
+
+def leg_run5(a):
+    import torch
+    import bench
+    from spgg_amd.engine import BatchEngine
+    every = int(a.variant)
+    _desc, L, M2, state, reps = bench.workload("cfg5", 0)
+    out = []
+    for _ in range(a.repeats + 1):
+        eng = BatchEngine(L, a.iters, reps, use_second_order=M2, state_representation=state, rng="mt19937")
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.run(snapshots=False, clusters_every=every, clusters_tiled=bool(every))
+            torch.cuda.synchronize()
+            out.append(time.perf_counter() - t0)
+            executed = eng.t - 1
+            if every:
+                eng.cluster_histories()   # (raises on a capped labelling)
+        finally:
+            eng.close()
+    return {"leg": "run5", "variant": a.variant, "iterations": executed, "L": L, "seconds": out[1:]}
 
 
 def leg_host(a):
@@ -287,7 +363,11 @@ RUN = (leg_run, ["0", "16", "1"])
 LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
                      "call": (leg_call, [f"{c}:{s}:{p}" for c in ("cfg3", "cfg4") for s in ("record", "sizes")
                                          for p in (0, 1)]),
-                     "run": (leg_run, ["0", "1", "16"])},
+                     "run": (leg_run, ["0", "1", "16"]),
+                     "tiled": (leg_tiled, [f"cfg5:{t}:{s}" for t in (32, 64, 128, 200) for s in ("record", "sizes")]
+                               + [f"{c}:{t}:record" for c in ("cfg4", "cfg3") for t in ("lds", 0, 32, 128)]),
+                     "host5": (leg_host5, ["cfg5"]),
+                     "run5": (leg_run5, ["0", "256", "16"])},
         "correlations": {"call": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN},
         "reputation": {"hist": (leg_call, SHAPES), "pairs": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN},
         "dwell": {"run": (leg_dwell_run, [f"{c}:{e}:{i}" for c in SHAPES for i in ("iters", "400") for e in (0, 256, 16)]),
