@@ -4,6 +4,7 @@
 """
 from __future__ import annotations
 
+import glob
 import hashlib
 import os
 import subprocess
@@ -34,10 +35,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-munsafe-fp-atomics"]
 
 
-DEPS = SRC + [os.path.join(INC, "spgg_abi.h"), os.path.join(INC, "spgg_test.h"), os.path.join(PKG_DIR, "csrc", "spgg_device.h"),
-              os.path.join(PKG_DIR, "csrc", "spgg_mt.h"), os.path.join(PKG_DIR, "csrc", "spgg_clusters.h"),
-              os.path.join(PKG_DIR, "csrc", "spgg_correlations.h"), os.path.join(PKG_DIR, "csrc", "spgg_reputation.h"),
-              os.path.join(PKG_DIR, "csrc", "spgg_dwell.h"), os.path.join(PKG_DIR, "csrc", "spgg_clusters_tiled.h")]
+# Everything a translation unit may include: a header nobody listed cannot leave a stale library.
+DEPS = [f for pattern in (os.path.join(PKG_DIR, "csrc", "*.hip"), os.path.join(PKG_DIR, "csrc", "*.h"),
+                          os.path.join(INC, "*.h")) for f in sorted(glob.glob(pattern))]
 
 
 def build_id(defines=()):

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "spgg_abi.h"
+#include "spgg_observe.h"
 
 namespace spgg_cl {
 
@@ -24,8 +25,8 @@ constexpr int kMaxPasses = SPGG_CLUSTERS_MAX_PASSES;
 constexpr int kThreads = 1024;
 
 // Enqueue the labelling of every replica's S plane of iteration t (absorbed replicas: of their
-// absorbing iteration) on `s`.  sizes may be null (record only).  L <= kMaxSide (caller checks).
-void launch(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, int L, int t,
-            int periodic, int32_t* sizes, int32_t* rec, int64_t rec_stride, hipStream_t s);
+// absorbing iteration) on `s`.  sizes may be null (record only).  lat.L <= kMaxSide (caller checks).
+void launch(const spgg_obs::Lattices& lat, int t, int periodic, int32_t* sizes, int32_t* rec, int64_t rec_stride,
+            hipStream_t s);
 
 }  // namespace spgg_cl

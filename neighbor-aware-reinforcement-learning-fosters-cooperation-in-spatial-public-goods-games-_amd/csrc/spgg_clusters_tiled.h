@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "spgg_abi.h"
+#include "spgg_observe.h"
 
 namespace spgg_clt {
 
@@ -22,9 +23,8 @@ constexpr int kMaxTile = 200;
 // The library's choice (tile = 0): 16 KiB of LDS per workgroup, 256 workgroups for one L = 1000
 // replica (the sides tried).
 constexpr int kDefaultTile = 64;
-// Pass cap of the tile pass (a pass = one scan of the tile): a tile with its edge as a wall is a
-// lattice of at most side 200, so the cap of spgg_clusters holds for it.
-constexpr int kMaxPasses = SPGG_CLUSTERS_MAX_PASSES;
+// (Pass cap of the tile pass: SPGG_CLUSTERS_MAX_PASSES, spgg_label_lds.h.  A tile with its edge as
+// a wall is a lattice of at most side 200, so the cap of spgg_clusters holds for it.)
 // Retry cap of one seam union (a retry = an atomic minimum that met a word another workgroup had
 // lowered first).  Every retry goes on with two indices below the word it lost, so the number of
 // retries is bounded by the chain it descends, never by timing.
@@ -38,8 +38,7 @@ inline int64_t workspace_words(int64_t n) { return 2 * n + kFlagWords; }
 // Enqueue the labelling of every replica's S plane of iteration t (absorbed replicas: of their
 // absorbing iteration) on `s`: init, tile pass, seam pass, count, record.  8 <= tile <= 200
 // (caller checks); work [n_rep][workspace_words(L * L)]; sizes may be null (record only).
-void launch(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, int L, int t,
-            int periodic, int tile, int32_t* work, int32_t* sizes, int32_t* rec, int64_t rec_stride,
-            hipStream_t s);
+void launch(const spgg_obs::Lattices& lat, int t, int periodic, int tile, int32_t* work, int32_t* sizes, int32_t* rec,
+            int64_t rec_stride, hipStream_t s);
 
 }  // namespace spgg_clt

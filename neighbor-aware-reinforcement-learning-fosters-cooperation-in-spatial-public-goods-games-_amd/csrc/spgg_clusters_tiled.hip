@@ -8,8 +8,8 @@
 // Workspace of a replica (int32): parent[n], count[n], flags[kFlagWords].  Five launches:
 //   init    rec = {0, 0, 0}, flags = 0
 //   tile    one workgroup per tile x tile square (ragged at the right and bottom edge) labels it
-//           in LDS with the tile edge as a wall -- the scan / resolve / relabel scheme of
-//           spgg_clusters.hip on 16-bit local labels -- and writes, for every cell of the tile,
+//           in LDS with the tile edge as a wall -- the pass of spgg_label_lds.h on 16-bit local
+//           labels -- and writes, for every cell of the tile,
 //           parent[g] = the global raster index of the first cell of its tile cluster (row-major
 //           order in a tile agrees with the raster order, so that is the tile cluster's smallest
 //           index; g itself for a defector) and count[g] = 0
@@ -40,59 +40,27 @@
 // The count launch runs after the seam launch ended, so every link is visible to it; its own
 // halving writes only shorten paths.
 //
-// Termination, from the code alone: the LDS passes are capped at kMaxPasses, the swap loop as in
-// spgg_clusters.hip, every walk at n steps, every union at kMaxRetries, and a parent word
+// Termination, from the code alone: the LDS pass and its loops are capped (spgg_label_lds.h),
+// every walk at n steps, every union at kMaxRetries, and a parent word
 // outside 0 .. x ends the walk.  Any cap sets flags[F_FAIL]; the record launch then writes
 // n_clusters = -1 (the other two 0) and the host raises.  A tile that fails still writes
 // parent[g] = g for its cells, so later walks stay inside the plane.  Nothing waits for another
 // workgroup: no flag is polled, no barrier spans workgroups.
 #include "spgg_clusters_tiled.h"
 
+#include "spgg_label_lds.h"
+
 namespace spgg_clt {
 namespace {
 
-constexpr uint32_t kDefector = 0xffffu;   // reserved local label (a tile has at most 40,000 cells)
-constexpr int kSwapCap = 2 * 65536;
+using namespace spgg_obs;
+
 constexpr int kSeamThreads = 256;
 
 static_assert(kMaxTile * kMaxTile < (int)kDefector, "local labels must fit 16 bits beside the reserved value");
 
-enum { F_FAIL = 0 };                                  // flag words of a replica
-enum { W_CHANGED = 0, W_FAIL, W_COUNT = 8 };          // workgroup-shared words of the tile pass
-
-typedef uint16_t __attribute__((may_alias)) half_t;
-
-__device__ __forceinline__ uint32_t half_of(const uint32_t* words, int i) {
-  return reinterpret_cast<const half_t*>(words)[i];
-}
-
-__device__ __forceinline__ void set_half(uint32_t* words, int i, uint32_t v) {
-  reinterpret_cast<half_t*>(words)[i] = (half_t)v;
-}
-
-// ref[x] = min(ref[x], m) on a 16-bit half of an LDS word; true if this call lowered it.
-__device__ __forceinline__ bool lower_ref(uint32_t* ref, int x, uint32_t m, uint32_t* fail) {
-  uint32_t* w = ref + (x >> 1);
-  const int sh = (x & 1) * 16;
-  uint32_t old = *w;
-  for (int k = 0; k < kSwapCap; ++k) {
-    if (((old >> sh) & 0xffffu) <= m) return false;
-    const uint32_t want = (old & ~(0xffffu << sh)) | (m << sh);
-    const uint32_t seen = atomicCAS(w, old, want);
-    if (seen == old) return true;
-    old = seen;
-  }
-  *fail = 1u;
-  return false;
-}
-
-// the plane holding S_t of replica rep; a replica absorbed before t keeps its state in S_stop's plane
-__device__ __forceinline__ const uint8_t* plane_of(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter,
-                                                   int rep, int n, int t) {
-  const int stop = stop_iter ? stop_iter[rep] : 0;
-  const int tt = (stop == 0 || stop >= t) ? t : stop;
-  return (((tt - 1) & 1) ? S1 : S0) + (size_t)rep * n;
-}
+enum { F_FAIL = 0 };                   // flag words of a replica
+enum { W_COUNT = 8 };                  // workgroup-shared words of the tile pass (the labelling pass's)
 
 __device__ __forceinline__ int32_t aload(const int32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -152,7 +120,7 @@ __global__ __launch_bounds__(kThreads) void spgg_clusters_tiled_tile_kernel(
   const int tw = min(tile, L - x0), th = min(tile, L - y0);
   const int m = tw * th;
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const uint8_t* plane = plane_of(S0, S1, stop_iter, rep, n, t);
+  const uint8_t* plane = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
   int32_t* parent = work + rep * words;
   int32_t* count = parent + n;
   int32_t* flags = count + n;
@@ -165,63 +133,7 @@ __global__ __launch_bounds__(kThreads) void spgg_clusters_tiled_tile_kernel(
     set_half(ref, l, (uint32_t)l);
   }
   __syncthreads();
-  // every cooperator starts with the label of the first cell of its row run inside the tile
-  for (int ly = tid; ly < th; ly += nthr) {
-    uint32_t run = kDefector;
-    for (int l = ly * tw; l < (ly + 1) * tw; ++l) {
-      if (half_of(label, l) == kDefector) run = kDefector;
-      else if (run == kDefector) run = (uint32_t)l;
-      else set_half(label, l, run);
-    }
-  }
-  __syncthreads();
-
-  bool converged = false;
-  for (int pass = 0; pass < kMaxPasses; ++pass) {
-    // scan (reads label, lowers ref); the tile edge is a wall
-    bool lowered = false;
-    for (int l = tid; l < m; l += nthr) {
-      const uint32_t own = half_of(label, l);
-      if (own == kDefector) continue;
-      const int ly = l / tw, lx = l - ly * tw;
-      uint32_t mn = own;
-      if (ly > 0) mn = min(mn, half_of(label, l - tw));
-      if (ly < th - 1) mn = min(mn, half_of(label, l + tw));
-      if (lx > 0) mn = min(mn, half_of(label, l - 1));
-      if (lx < tw - 1) mn = min(mn, half_of(label, l + 1));
-      if (mn < own) lowered |= lower_ref(ref, (int)own, mn, &sh[W_FAIL]);
-    }
-    if (lowered) sh[W_CHANGED] = 1u;
-    __syncthreads();
-    const bool changed = sh[W_CHANGED] != 0u, failed = sh[W_FAIL] != 0u;   // workgroup-uniform
-    if (failed) break;
-    if (!changed) {
-      converged = true;
-      break;
-    }
-    // resolve (reads ref, writes label[x] of this thread's representatives)
-    for (int x = tid; x < m; x += nthr) {
-      if (half_of(label, x) != (uint32_t)x) continue;
-      uint32_t r = half_of(ref, x);
-      if (r == (uint32_t)x) continue;
-      int k = 0;
-      for (; k < m; ++k) {   // ref[r] < r until the root: at most m steps
-        const uint32_t q = half_of(ref, (int)r);
-        if (q >= r) break;
-        r = q;
-      }
-      if (k == m) sh[W_FAIL] = 1u;
-      set_half(label, x, r);
-    }
-    __syncthreads();
-    if (tid == 0) sh[W_CHANGED] = 0u;   // (read above, before the barrier; next written after the next one)
-    // relabel
-    for (int l = tid; l < m; l += nthr) {
-      const uint32_t lb = half_of(label, l);
-      if (lb != kDefector && lb < (uint32_t)m) set_half(label, l, half_of(label, (int)lb));
-    }
-    __syncthreads();
-  }
+  const bool converged = label_region(label, ref, sh, tw, th, false);   // the tile edge is a wall
   if (!converged && tid == 0) set_fail(flags);   // the pass cap (or an unreachable loop cap)
 
   for (int l = tid; l < m; l += nthr) {
@@ -250,7 +162,7 @@ __global__ __launch_bounds__(kSeamThreads) void spgg_clusters_tiled_seam_kernel(
   const long long pairs = 2LL * nseam * L;
   const long long p = (long long)blockIdx.x * kSeamThreads + threadIdx.x;
   if (p >= pairs) return;
-  const uint8_t* plane = plane_of(S0, S1, stop_iter, rep, n, t);
+  const uint8_t* plane = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
   int32_t* parent = work + rep * words;
   int32_t* flags = parent + 2LL * n;
 
@@ -285,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void spgg_clusters_tiled_count_kernel(
   const int rep = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long gl = (long long)blockIdx.x * kThreads + tid;
-  const uint8_t* plane = plane_of(S0, S1, stop_iter, rep, n, t);
+  const uint8_t* plane = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
   int32_t* parent = work + rep * words;
   int32_t* count = parent + n;
   int32_t* flags = count + n;
@@ -331,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void spgg_clusters_tiled_record_kernel(
   const int rep = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63;
   const long long gl = (long long)blockIdx.x * kThreads + tid;
-  const uint8_t* plane = plane_of(S0, S1, stop_iter, rep, n, t);
+  const uint8_t* plane = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
   const int32_t* parent = work + rep * words;
   const int32_t* count = parent + n;
   const int32_t* flags = count + n;
@@ -355,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void spgg_clusters_tiled_record_kernel(
     }
     if (sizes) sizes[(size_t)rep * n + g] = sz;
   }
-  for (int off = 32; off > 0; off >>= 1) {
+  for (int off = 32; off > 0; off >>= 1) {   // lane 0's total only (fewer instructions than wave_sum's butterfly)
     nclu += __shfl_down(nclu, off, 64);
     bonds += __shfl_down(bonds, off, 64);
     largest = max(largest, __shfl_down(largest, off, 64));
@@ -381,17 +293,20 @@ __global__ __launch_bounds__(kThreads) void spgg_clusters_tiled_record_kernel(
 }
 
 template <int kSide>
-void launch_tiles(dim3 grid, int threads, hipStream_t s, const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter,
-                  int L, int t, int tile, int ntx, int32_t* work, long long words) {
-  hipLaunchKernelGGL(spgg_clusters_tiled_tile_kernel<kSide>, grid, dim3(threads), 0, s, S0, S1, stop_iter, L, t, tile,
-                     ntx, work, words);
+void launch_tiles(dim3 grid, int threads, hipStream_t s, const Lattices& lat, int t, int tile, int ntx, int32_t* work,
+                  long long words) {
+  hipLaunchKernelGGL(spgg_clusters_tiled_tile_kernel<kSide>, grid, dim3(threads), 0, s, lat.S0, lat.S1, lat.stop_iter,
+                     lat.L, t, tile, ntx, work, words);
 }
 
 }  // namespace
 
-void launch(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, int L, int t, int periodic,
-            int tile, int32_t* work, int32_t* sizes, int32_t* rec, int64_t rec_stride, hipStream_t s) {
-  const long long n = (long long)L * L;
+void launch(const spgg_obs::Lattices& lat, int t, int periodic, int tile, int32_t* work, int32_t* sizes, int32_t* rec,
+            int64_t rec_stride, hipStream_t s) {
+  const uint8_t *S0 = lat.S0, *S1 = lat.S1;
+  const int32_t* stop_iter = lat.stop_iter;
+  const int n_rep = lat.n_rep, L = lat.L;
+  const long long n = lat.cells();
   const long long words = workspace_words(n);
   const int ntx = (L + tile - 1) / tile;
   periodic = periodic ? 1 : 0;
@@ -402,10 +317,10 @@ void launch(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int 
   const int cells = side * side;
   const int threads = cells >= kThreads ? kThreads : ((cells + 63) / 64) * 64;   // whole waves
   const dim3 tiles(ntx * ntx, n_rep);
-  if (side <= 32) launch_tiles<32>(tiles, threads, s, S0, S1, stop_iter, L, t, side, ntx, work, words);
-  else if (side <= 64) launch_tiles<64>(tiles, threads, s, S0, S1, stop_iter, L, t, side, ntx, work, words);
-  else if (side <= 128) launch_tiles<128>(tiles, threads, s, S0, S1, stop_iter, L, t, side, ntx, work, words);
-  else launch_tiles<kMaxTile>(tiles, threads, s, S0, S1, stop_iter, L, t, side, ntx, work, words);
+  if (side <= 32) launch_tiles<32>(tiles, threads, s, lat, t, side, ntx, work, words);
+  else if (side <= 64) launch_tiles<64>(tiles, threads, s, lat, t, side, ntx, work, words);
+  else if (side <= 128) launch_tiles<128>(tiles, threads, s, lat, t, side, ntx, work, words);
+  else launch_tiles<kMaxTile>(tiles, threads, s, lat, t, side, ntx, work, words);
   const long long pairs = 2LL * (ntx - 1 + periodic) * L;
   if (pairs > 0)   // (one tile with walls has no seam: decided by the arguments, never by the data)
     hipLaunchKernelGGL(spgg_clusters_tiled_seam_kernel, dim3((unsigned)((pairs + kSeamThreads - 1) / kSeamThreads), n_rep),

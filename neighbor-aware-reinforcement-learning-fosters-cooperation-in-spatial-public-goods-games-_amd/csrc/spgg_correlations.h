@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "spgg_abi.h"
+#include "spgg_observe.h"
 
 namespace spgg_co {
 
@@ -43,7 +44,6 @@ static_assert(2ll * kMaxSide * kMaxSide < (1ll << 31), "counts must fit int32");
 // Enqueue the pair counts of every replica's S plane of iteration t (absorbed replicas: of their
 // absorbing iteration) on `s`: replica k's rows[0..max_d], cols[0..max_d] at out + k*out_stride.
 // 1 <= L <= kMaxSide and 0 <= max_d <= L / 2 (caller checks).
-void launch(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, int L, int t,
-            int max_d, int32_t* out, int64_t out_stride, hipStream_t s);
+void launch(const spgg_obs::Lattices& lat, int t, int max_d, int32_t* out, int64_t out_stride, hipStream_t s);
 
 }  // namespace spgg_co

@@ -29,11 +29,7 @@
 namespace spgg_co {
 namespace {
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-  return v;
-}
+using namespace spgg_obs;
 
 // the value of the lane a DPP control selects (every lane active: the callers' loops are wave-uniform)
 template <int CTRL>
@@ -53,11 +49,8 @@ __global__ __launch_bounds__(kThreads) void spgg_correlations_kernel(
   const int n = L * L;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // the plane holding S_t; a replica absorbed before t keeps its state in S_stop's plane
-  const int stop = stop_iter ? stop_iter[rep] : 0;
-  const int tt = (stop == 0 || stop >= t) ? t : stop;
   // replica planes are n bytes apart: for odd L not 4-byte aligned
-  const uint8_t* plane = (((tt - 1) & 1) ? S1 : S0) + (size_t)rep * n;
+  const uint8_t* plane = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
 
   // pack: a wave takes 256 cells of a row at a time, a lane 4 of them (one unaligned 4-byte
   // load, single bytes at the row's end), 8 lanes make a word; kPackDepth rows per trip, their
@@ -139,15 +132,12 @@ __global__ __launch_bounds__(kThreads) void spgg_correlations_kernel(
 
 }  // namespace
 
-void launch(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, int L, int t,
-            int max_d, int32_t* out, int64_t out_stride, hipStream_t s) {
-  const dim3 grid((max_d + kDistPerGroup) / kDistPerGroup, n_rep);
-  if (lattice_words(L) <= kSmallWords)
-    hipLaunchKernelGGL(spgg_correlations_kernel<kSmallWords>, grid, dim3(kThreads), 0, s, S0, S1, stop_iter, L, t,
-                       max_d, out, (long long)out_stride);
-  else
-    hipLaunchKernelGGL(spgg_correlations_kernel<kFullWords>, grid, dim3(kThreads), 0, s, S0, S1, stop_iter, L, t,
-                       max_d, out, (long long)out_stride);
+void launch(const spgg_obs::Lattices& lat, int t, int max_d, int32_t* out, int64_t out_stride, hipStream_t s) {
+  const dim3 grid((max_d + kDistPerGroup) / kDistPerGroup, lat.n_rep);
+  const auto kernel = lattice_words(lat.L) <= kSmallWords ? spgg_correlations_kernel<kSmallWords>
+                                                          : spgg_correlations_kernel<kFullWords>;
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, s, lat.S0, lat.S1, lat.stop_iter, lat.L, t, max_d, out,
+                     (long long)out_stride);
 }
 
 }  // namespace spgg_co

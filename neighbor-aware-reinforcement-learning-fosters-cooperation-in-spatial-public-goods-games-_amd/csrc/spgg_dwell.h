@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "spgg_abi.h"
+#include "spgg_observe.h"
 
 namespace spgg_dw {
 
@@ -39,21 +40,18 @@ static_assert((long long)kCells << kMaxIterLog2 > (1ll << 32), "why the two sums
 
 // ref = S_{t_ref} & 1 and words = (0, t_ref, 0) of every agent, from plane (t_ref - 1) & 1 (an
 // absorbed replica: the plane of its absorbing iteration).
-void launch_reset(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int t_ref,
-                  uint32_t* words, uint8_t* ref, hipStream_t s);
+void launch_reset(const spgg_obs::Lattices& lat, int t_ref, uint32_t* words, uint8_t* ref, hipStream_t s);
 
 // After the step launch of iteration j (S_j in plane (j - 1) & 1, S_{j+1} in plane j & 1): the
 // words of every agent whose strategy changed.  Replicas absorbed at or before j are skipped.
-void launch_step(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int j,
-                 uint32_t* words, hipStream_t s);
+void launch_step(const spgg_obs::Lattices& lat, int j, uint32_t* words, hipStream_t s);
 
 // The kSlots-value row of S_t per replica (a zeroing launch, then one that adds into it).
-void launch_record(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int t,
-                   int t_ref, const uint32_t* words, const uint8_t* ref, long long* out, int64_t out_stride,
-                   hipStream_t s);
+void launch_record(const spgg_obs::Lattices& lat, int t, int t_ref, const uint32_t* words, const uint8_t* ref,
+                   long long* out, int64_t out_stride, hipStream_t s);
 
 // The per-agent fields flips, age, coop of S_t: int32 [3][n] per replica.
-void launch_fields(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int t,
-                   int t_ref, const uint32_t* words, int32_t* out, int64_t out_stride, hipStream_t s);
+void launch_fields(const spgg_obs::Lattices& lat, int t, int t_ref, const uint32_t* words, int32_t* out,
+                   int64_t out_stride, hipStream_t s);
 
 }  // namespace spgg_dw

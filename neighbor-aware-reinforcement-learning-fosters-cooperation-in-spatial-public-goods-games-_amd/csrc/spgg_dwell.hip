@@ -34,27 +34,19 @@ struct Words {
 };
 static_assert(sizeof(Words) == 4 * kWords && alignof(Words) == 4, "[n_rep][n][3] uint32");
 
+using namespace spgg_obs;
+
 // the state index a read-out of t describes: a replica absorbed at s < t stays at S_s (and one
 // absorbed before tracking began at S_{t_ref} = S_s)
 __device__ __forceinline__ int state_of(const int32_t* stop_iter, int rep, int t, int t_ref) {
-  const int stop = stop_iter[rep];
-  const int tt = (stop == 0 || stop >= t) ? t : stop;
-  return tt < t_ref ? t_ref : tt;
-}
-
-// the plane of S_t; an absorbed replica keeps its state in the plane of its absorbing iteration
-__device__ __forceinline__ const uint8_t* plane_of(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter,
-                                                   int rep, int t) {
-  const int stop = stop_iter[rep];
-  const int tt = (stop == 0 || stop >= t) ? t : stop;
-  return ((tt - 1) & 1) ? S1 : S0;
+  return max(t_ref, observed_iter(stop_iter, rep, t));
 }
 
 __global__ __launch_bounds__(kThreads) void spgg_dwell_reset_kernel(
     const uint8_t* __restrict__ S0, const uint8_t* __restrict__ S1, const int32_t* __restrict__ stop_iter, int n,
     int t_ref, Words* __restrict__ words, uint8_t* __restrict__ ref) {
   const int rep = blockIdx.y;
-  const uint8_t* sp = plane_of(S0, S1, stop_iter, rep, t_ref) + (size_t)rep * n;
+  const uint8_t* sp = observed_plane(S0, S1, stop_iter, rep, t_ref) + (size_t)rep * n;
   const int base = blockIdx.x * kCells;
 #pragma unroll 4
   for (int u = 0; u < kCells / kThreads; ++u) {
@@ -134,18 +126,6 @@ __global__ __launch_bounds__(kThreads) void spgg_dwell_zero_kernel(long long* __
   for (int i = threadIdx.x; i < kSlots; i += kThreads) out[(long long)blockIdx.x * out_stride + i] = 0;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kThreads) void spgg_dwell_record_kernel(
     const uint8_t* __restrict__ S0, const uint8_t* __restrict__ S1, const int32_t* __restrict__ stop_iter, int n, int t,
     int t_ref, const Words* __restrict__ words, const uint8_t* __restrict__ ref, unsigned long long* __restrict__ out,
@@ -156,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void spgg_dwell_record_kernel(
   const int rep = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t te = (uint32_t)state_of(stop_iter, rep, t, t_ref);
-  const uint8_t* sp = plane_of(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
+  const uint8_t* sp = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
   const uint8_t* rp = ref + (size_t)rep * n;
   const Words* wp = words + (size_t)rep * n;
 
@@ -204,7 +184,7 @@ __global__ __launch_bounds__(kThreads) void spgg_dwell_fields_kernel(
     int t_ref, const Words* __restrict__ words, int32_t* __restrict__ out, long long out_stride) {
   const int rep = blockIdx.y;
   const uint32_t te = (uint32_t)state_of(stop_iter, rep, t, t_ref);
-  const uint8_t* sp = plane_of(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
+  const uint8_t* sp = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;
   const Words* wp = words + (size_t)rep * n;
   int32_t* o = out + (long long)rep * out_stride;
   const int base = blockIdx.x * kCells;
@@ -220,42 +200,37 @@ __global__ __launch_bounds__(kThreads) void spgg_dwell_fields_kernel(
   }
 }
 
-inline dim3 readout_grid(long long n, int n_rep) { return dim3((unsigned)((n + kCells - 1) / kCells), n_rep); }
+inline dim3 readout_grid(const Lattices& lat) { return dim3((unsigned)((lat.cells() + kCells - 1) / kCells), lat.n_rep); }
 
 }  // namespace
 
-void launch_reset(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int t_ref,
-                  uint32_t* words, uint8_t* ref, hipStream_t s) {
-  hipLaunchKernelGGL(spgg_dwell_reset_kernel, readout_grid(n, n_rep), dim3(kThreads), 0, s, S0, S1, stop_iter, (int)n,
-                     t_ref, reinterpret_cast<Words*>(words), ref);
+void launch_reset(const spgg_obs::Lattices& lat, int t_ref, uint32_t* words, uint8_t* ref, hipStream_t s) {
+  hipLaunchKernelGGL(spgg_dwell_reset_kernel, readout_grid(lat), dim3(kThreads), 0, s, lat.S0, lat.S1, lat.stop_iter,
+                     (int)lat.cells(), t_ref, reinterpret_cast<Words*>(words), ref);
 }
 
-void launch_step(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int j,
-                 uint32_t* words, hipStream_t s) {
-  const dim3 grid((unsigned)((n + kStepCells - 1) / kStepCells), n_rep);
+void launch_step(const spgg_obs::Lattices& lat, int j, uint32_t* words, hipStream_t s) {
+  const long long n = lat.cells();
+  const dim3 grid((unsigned)((n + kStepCells - 1) / kStepCells), lat.n_rep);
   // dword loads need every replica base rep * n (and the caller's planes: spgg_dwell_bind) aligned
-  const bool aligned = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(S0) | reinterpret_cast<uintptr_t>(S1)) & 3) == 0;
-  if (aligned)
-    hipLaunchKernelGGL(spgg_dwell_step_kernel<true>, grid, dim3(kThreads), 0, s, S0, S1, stop_iter, (int)n, j,
-                       reinterpret_cast<Words*>(words));
-  else
-    hipLaunchKernelGGL(spgg_dwell_step_kernel<false>, grid, dim3(kThreads), 0, s, S0, S1, stop_iter, (int)n, j,
-                       reinterpret_cast<Words*>(words));
+  const bool aligned =
+      n % 4 == 0 && ((reinterpret_cast<uintptr_t>(lat.S0) | reinterpret_cast<uintptr_t>(lat.S1)) & 3) == 0;
+  hipLaunchKernelGGL(aligned ? spgg_dwell_step_kernel<true> : spgg_dwell_step_kernel<false>, grid, dim3(kThreads), 0, s,
+                     lat.S0, lat.S1, lat.stop_iter, (int)n, j, reinterpret_cast<Words*>(words));
 }
 
-void launch_record(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int t,
-                   int t_ref, const uint32_t* words, const uint8_t* ref, long long* out, int64_t out_stride,
-                   hipStream_t s) {
-  hipLaunchKernelGGL(spgg_dwell_zero_kernel, dim3(n_rep), dim3(kThreads), 0, s, out, (long long)out_stride);
-  hipLaunchKernelGGL(spgg_dwell_record_kernel, readout_grid(n, n_rep), dim3(kThreads), 0, s, S0, S1, stop_iter, (int)n,
-                     t, t_ref, reinterpret_cast<const Words*>(words), ref, reinterpret_cast<unsigned long long*>(out),
-                     (long long)out_stride);
+void launch_record(const spgg_obs::Lattices& lat, int t, int t_ref, const uint32_t* words, const uint8_t* ref,
+                   long long* out, int64_t out_stride, hipStream_t s) {
+  hipLaunchKernelGGL(spgg_dwell_zero_kernel, dim3(lat.n_rep), dim3(kThreads), 0, s, out, (long long)out_stride);
+  hipLaunchKernelGGL(spgg_dwell_record_kernel, readout_grid(lat), dim3(kThreads), 0, s, lat.S0, lat.S1, lat.stop_iter,
+                     (int)lat.cells(), t, t_ref, reinterpret_cast<const Words*>(words), ref,
+                     reinterpret_cast<unsigned long long*>(out), (long long)out_stride);
 }
 
-void launch_fields(const uint8_t* S0, const uint8_t* S1, const int32_t* stop_iter, int n_rep, long long n, int t,
-                   int t_ref, const uint32_t* words, int32_t* out, int64_t out_stride, hipStream_t s) {
-  hipLaunchKernelGGL(spgg_dwell_fields_kernel, readout_grid(n, n_rep), dim3(kThreads), 0, s, S0, S1, stop_iter, (int)n,
-                     t, t_ref, reinterpret_cast<const Words*>(words), out, (long long)out_stride);
+void launch_fields(const spgg_obs::Lattices& lat, int t, int t_ref, const uint32_t* words, int32_t* out,
+                   int64_t out_stride, hipStream_t s) {
+  hipLaunchKernelGGL(spgg_dwell_fields_kernel, readout_grid(lat), dim3(kThreads), 0, s, lat.S0, lat.S1, lat.stop_iter,
+                     (int)lat.cells(), t, t_ref, reinterpret_cast<const Words*>(words), out, (long long)out_stride);
 }
 
 }  // namespace spgg_dw

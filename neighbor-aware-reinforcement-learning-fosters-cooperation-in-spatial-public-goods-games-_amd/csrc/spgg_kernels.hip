@@ -3531,6 +3531,11 @@ static int seg_end(const spgg_ctx* c, int t, int end) {
   return t1;
 }
 
+// The leading arguments of every observer launch (spgg_observe.h).
+static spgg_obs::Lattices lattices(const spgg_ctx* c) {
+  return {c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L};
+}
+
 // Iterations t .. t1 of a spgg_step call that began at t0: their generator chunks (MT19937) and
 // the step launch(es) -- one per iteration, or one persistent launch.
 static void step_seg(spgg_ctx* c, int t, int t1, int32_t t0, hipStream_t s) {
@@ -3549,7 +3554,7 @@ static void step_seg(spgg_ctx* c, int t, int t1, int32_t t0, hipStream_t s) {
     if (t1 > t) launch_persist(c, t, t1, s);
     else launch_step(c, t, 0, s);
     if (c->dwell_armed && t >= c->dwell_t_ref)   // (never with persistent launches: spgg_dwell_bind)
-      spgg_dw::launch_step(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t, c->dwell_words, s);
+      spgg_dw::launch_step(lattices(c), t, c->dwell_words, s);
   }
   if (mt && (t1 % K == 0 || t1 == T)) (void)hipEventRecord(c->step_done[((t1 - 1) / K) & 1], s);
 }
@@ -3679,8 +3684,7 @@ int spgg_clusters(spgg_ctx* c, int32_t t, int32_t periodic, int32_t* sizes, int3
                   void* stream) {
   if (const int rc = observable_check(c, "spgg_clusters", rec, false, t)) return rc;
   if (const int rc = range_check(c, "spgg_clusters", spgg_cl::kMaxSide, "the lattice is labelled in LDS")) return rc;
-  spgg_cl::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, periodic, sizes, rec,
-                        rec_stride, reinterpret_cast<hipStream_t>(stream));
+  spgg_cl::launch(lattices(c), t, periodic, sizes, rec, rec_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_clusters launch");
 }
 
@@ -3698,8 +3702,7 @@ int spgg_clusters_tiled(spgg_ctx* c, int32_t t, int32_t periodic, int32_t tile, 
     return fail(c, SPGG_E_ARG, "spgg_clusters_tiled: tile = " + std::to_string(tile) + " outside " +
                                    std::to_string(spgg_clt::kMinTile) + " .. " + std::to_string(spgg_clt::kMaxTile) +
                                    " (0: the library's choice)");
-  spgg_clt::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, periodic, tile, work, sizes,
-                   rec, rec_stride, reinterpret_cast<hipStream_t>(stream));
+  spgg_clt::launch(lattices(c), t, periodic, tile, work, sizes, rec, rec_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_clusters_tiled launch");
 }
 
@@ -3711,8 +3714,7 @@ int spgg_correlations(spgg_ctx* c, int32_t t, int32_t max_d, int32_t* out, int64
   if (const int rc = observable_check(c, "spgg_correlations", out, false, t)) return rc;
   if (const int rc = range_check(c, "spgg_correlations", spgg_co::kMaxSide, "the lattice is packed into LDS", max_d))
     return rc;
-  spgg_co::launch(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, max_d, out, out_stride,
-                  reinterpret_cast<hipStream_t>(stream));
+  spgg_co::launch(lattices(c), t, max_d, out, out_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_correlations launch");
 }
 
@@ -3728,9 +3730,8 @@ int spgg_reputation_hist(spgg_ctx* c, int32_t t, int32_t bins, const double* edg
                                    std::to_string(spgg_rp::kMaxBins));
   if (out_stride < 2 * (int64_t)bins)
     return fail(c, SPGG_E_ARG, "spgg_reputation_hist: out_stride below 2 * bins");
-  spgg_rp::launch_hist(c->buf.S[0], c->buf.S[1], c->buf.R[0], c->buf.R[1], c->cfg.rep_int8 != 0, c->d_params,
-                       c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, bins, edges, out, out_stride,
-                       reinterpret_cast<hipStream_t>(stream));
+  spgg_rp::launch_hist(lattices(c), c->buf.R[0], c->buf.R[1], c->cfg.rep_int8 != 0, c->d_params, t, bins, edges, out,
+                       out_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_reputation_hist launch");
 }
 
@@ -3742,9 +3743,8 @@ int spgg_reputation_pairs(spgg_ctx* c, int32_t t, int32_t max_d, int64_t* out, i
   if (const int rc = range_check(c, "spgg_reputation_pairs", spgg_rp::kMaxSide, "int32 lane partials", max_d)) return rc;
   if (out_stride < 2 * (int64_t)(max_d + 1) + 1)
     return fail(c, SPGG_E_ARG, "spgg_reputation_pairs: out_stride below 2 * (max_d + 1) + 1");
-  spgg_rp::launch_pairs(static_cast<const int8_t*>(c->buf.R[0]), static_cast<const int8_t*>(c->buf.R[1]),
-                        c->buf.stop_iter, c->cfg.n_rep, c->cfg.L, t, max_d, reinterpret_cast<long long*>(out), out_stride,
-                        reinterpret_cast<hipStream_t>(stream));
+  spgg_rp::launch_pairs(lattices(c), static_cast<const int8_t*>(c->buf.R[0]), static_cast<const int8_t*>(c->buf.R[1]), t,
+                        max_d, reinterpret_cast<long long*>(out), out_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_reputation_pairs launch");
 }
 
@@ -3766,8 +3766,7 @@ int spgg_dwell_reset(spgg_ctx* c, int32_t t_ref, void* stream) {
   if (const int rc = observable_check(c, "spgg_dwell_reset", true, false, t_ref)) return rc;
   if (!c->dwell_words) return fail(c, SPGG_E_STATE, "spgg_dwell_reset before spgg_dwell_bind");
   if (t_ref > c->cfg.iterations + 1) return fail(c, SPGG_E_ARG, "spgg_dwell_reset: t_ref beyond iterations + 1");
-  spgg_dw::launch_reset(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t_ref, c->dwell_words,
-                        c->dwell_ref, reinterpret_cast<hipStream_t>(stream));
+  spgg_dw::launch_reset(lattices(c), t_ref, c->dwell_words, c->dwell_ref, reinterpret_cast<hipStream_t>(stream));
   c->dwell_armed = true;
   c->dwell_t_ref = t_ref;
   return hip_check(c, hipGetLastError(), "spgg_dwell_reset launch");
@@ -3786,16 +3785,15 @@ static int dwell_check(spgg_ctx* c, const char* fn, const void* out, int32_t t, 
 
 int spgg_dwell_record(spgg_ctx* c, int32_t t, int64_t* out, int64_t out_stride, void* stream) {
   if (const int rc = dwell_check(c, "spgg_dwell_record", out, t, out_stride, SPGG_DWELL_SLOTS)) return rc;
-  spgg_dw::launch_record(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t, c->dwell_t_ref,
-                         c->dwell_words, c->dwell_ref, reinterpret_cast<long long*>(out), out_stride,
-                         reinterpret_cast<hipStream_t>(stream));
+  spgg_dw::launch_record(lattices(c), t, c->dwell_t_ref, c->dwell_words, c->dwell_ref, reinterpret_cast<long long*>(out),
+                         out_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_dwell_record launch");
 }
 
 int spgg_dwell_fields(spgg_ctx* c, int32_t t, int32_t* out, int64_t out_stride, void* stream) {
   if (const int rc = dwell_check(c, "spgg_dwell_fields", out, t, out_stride, c ? 3 * (int64_t)c->n : 0)) return rc;
-  spgg_dw::launch_fields(c->buf.S[0], c->buf.S[1], c->buf.stop_iter, c->cfg.n_rep, c->n, t, c->dwell_t_ref,
-                         c->dwell_words, out, out_stride, reinterpret_cast<hipStream_t>(stream));
+  spgg_dw::launch_fields(lattices(c), t, c->dwell_t_ref, c->dwell_words, out, out_stride,
+                         reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_dwell_fields launch");
 }
 

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "spgg_abi.h"
+#include "spgg_observe.h"
 
 namespace spgg_rp {
 
@@ -86,14 +87,14 @@ static_assert((long long)kMaxSide * kMaxSide < (1ll << 31), "cell indices fit in
 // of their absorbing iteration) on `s`: a launch that zeroes each replica's 2 * bins counts, then
 // one that adds into them.  rep_int8: R holds int8 multiples of params[rep].rep_unit, else f64.
 // 1 <= bins <= kMaxBins, out_stride >= 2 * bins (caller checks).
-void launch_hist(const uint8_t* S0, const uint8_t* S1, const void* R0, const void* R1, bool rep_int8,
-                 const spgg_rep_params* params, const int32_t* stop_iter, int n_rep, int L, int t, int bins,
-                 const double* edges, int32_t* out, int64_t out_stride, hipStream_t s);
+void launch_hist(const spgg_obs::Lattices& lat, const void* R0, const void* R1, bool rep_int8,
+                 const spgg_rep_params* params, int t, int bins, const double* edges, int32_t* out,
+                 int64_t out_stride, hipStream_t s);
 
 // Enqueue the pair sums of every replica's int8 R plane of iteration t on `s`: replica k's sum,
 // rows[0..max_d], cols[0..max_d] at out + k*out_stride.  1 <= L <= kMaxSide and
 // 0 <= max_d <= L / 2 (caller checks).
-void launch_pairs(const int8_t* R0, const int8_t* R1, const int32_t* stop_iter, int n_rep, int L, int t,
-                  int max_d, long long* out, int64_t out_stride, hipStream_t s);
+void launch_pairs(const spgg_obs::Lattices& lat, const int8_t* R0, const int8_t* R1, int t, int max_d, long long* out,
+                  int64_t out_stride, hipStream_t s);
 
 }  // namespace spgg_rp

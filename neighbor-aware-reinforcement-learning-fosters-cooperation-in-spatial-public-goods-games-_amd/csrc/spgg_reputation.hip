@@ -40,22 +40,10 @@
 namespace spgg_rp {
 namespace {
 
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+using namespace spgg_obs;
 
 __device__ __forceinline__ int dot4(uint32_t a, uint32_t b, int acc) {
   return __builtin_amdgcn_sdot4((int)a, (int)b, acc, false);
-}
-
-// the plane index of S_t / R_t; a replica absorbed before t keeps its state in the plane of its
-// absorbing iteration
-__device__ __forceinline__ int plane_of(const int32_t* stop_iter, int rep, int t) {
-  const int stop = stop_iter ? stop_iter[rep] : 0;
-  const int tt = (stop == 0 || stop >= t) ? t : stop;
-  return (tt - 1) & 1;
 }
 
 // ---- histogram ---------------------------------------------------------------------------
@@ -93,8 +81,8 @@ __global__ __launch_bounds__(kHistThreads) void spgg_reputation_hist_kernel(
   const int rep = blockIdx.y;
   const int n = L * L;
   const int tid = threadIdx.x, wave = tid >> 6;
-  const int pl = plane_of(stop_iter, rep, t);
-  const uint8_t* sp = (pl ? S1 : S0) + (size_t)rep * n;   // n bytes apart: unaligned for odd L
+  const uint8_t* sp = observed_plane(S0, S1, stop_iter, rep, t) + (size_t)rep * n;   // n bytes apart: unaligned for odd L
+  const void* rv = observed_plane(R0, R1, stop_iter, rep, t);                        // R_t lies where S_t does
 
   for (int i = tid; i <= bins; i += kHistThreads) e[i] = edges[(size_t)rep * (bins + 1) + i];
   for (int i = tid; i < kHistWaves * 2 * kMaxBins; i += kHistThreads) (&h[0][0])[i] = 0u;
@@ -106,7 +94,7 @@ __global__ __launch_bounds__(kHistThreads) void spgg_reputation_hist_kernel(
     // x = k * rep_unit is an exact product; kHistThreads == the 256 levels
     level_bin[tid] = (int16_t)bin_of(e, bins, (double)(tid - 128) * params[rep].rep_unit);
     __syncthreads();
-    const int8_t* rp = (const int8_t*)(pl ? R1 : R0) + (size_t)rep * n;
+    const int8_t* rp = (const int8_t*)rv + (size_t)rep * n;
 #pragma unroll
     for (int j = 0; j < kHistCells / (4 * kHistThreads); ++j) {
       const int i = base + (j * kHistThreads + tid) * 4;
@@ -131,7 +119,7 @@ __global__ __launch_bounds__(kHistThreads) void spgg_reputation_hist_kernel(
       }
     }
   } else {
-    const double* rp = (const double*)(pl ? R1 : R0) + (size_t)rep * n;
+    const double* rp = (const double*)rv + (size_t)rep * n;
 #pragma unroll 4
     for (int j = 0; j < kHistCells / kHistThreads; ++j) {
       const int i = base + j * kHistThreads + tid;
@@ -177,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void spgg_reputation_pairs_lds_kernel(
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // replica planes are n bytes apart: for odd L not 4-byte aligned
-  const int8_t* plane = (plane_of(stop_iter, rep, t) ? R1 : R0) + (size_t)rep * n;
+  const int8_t* plane = observed_plane(R0, R1, stop_iter, rep, t) + (size_t)rep * n;
 
   // stage: a wave takes 256 cells of a row at a time, a lane 4 of them; kStageDepth rows per
   // trip, their loads issued before the first is stored
@@ -264,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void spgg_reputation_pairs_global_kernel(
   const size_t n = (size_t)L * L;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int8_t* plane = (plane_of(stop_iter, rep, t) ? R1 : R0) + (size_t)rep * n;
+  const int8_t* plane = observed_plane(R0, R1, stop_iter, rep, t) + (size_t)rep * n;
   const bool cols = (int)blockIdx.x > max_d;               // pairs 0 .. max_d: rows, then columns
   const int d = cols ? (int)blockIdx.x - (max_d + 1) : (int)blockIdx.x;
   const bool with_sum = blockIdx.x == 0;                   // the workgroup of rows[0] also sums the plane
@@ -319,35 +307,29 @@ __global__ __launch_bounds__(kThreads) void spgg_reputation_pairs_global_kernel(
 
 }  // namespace
 
-void launch_hist(const uint8_t* S0, const uint8_t* S1, const void* R0, const void* R1, bool rep_int8,
-                 const spgg_rep_params* params, const int32_t* stop_iter, int n_rep, int L, int t, int bins,
-                 const double* edges, int32_t* out, int64_t out_stride, hipStream_t s) {
-  hipLaunchKernelGGL(spgg_reputation_zero_kernel, dim3(n_rep), dim3(kHistThreads), 0, s, out, (long long)out_stride,
-                     2 * bins);
-  const long long n = (long long)L * L;
-  const dim3 grid((unsigned)((n + kHistCells - 1) / kHistCells), n_rep);
-  if (rep_int8)
-    hipLaunchKernelGGL(spgg_reputation_hist_kernel<true>, grid, dim3(kHistThreads), 0, s, S0, S1, R0, R1, params,
-                       stop_iter, L, t, bins, edges, out, (long long)out_stride);
-  else
-    hipLaunchKernelGGL(spgg_reputation_hist_kernel<false>, grid, dim3(kHistThreads), 0, s, S0, S1, R0, R1, params,
-                       stop_iter, L, t, bins, edges, out, (long long)out_stride);
+void launch_hist(const spgg_obs::Lattices& lat, const void* R0, const void* R1, bool rep_int8,
+                 const spgg_rep_params* params, int t, int bins, const double* edges, int32_t* out,
+                 int64_t out_stride, hipStream_t s) {
+  hipLaunchKernelGGL(spgg_reputation_zero_kernel, dim3(lat.n_rep), dim3(kHistThreads), 0, s, out,
+                     (long long)out_stride, 2 * bins);
+  const dim3 grid((unsigned)((lat.cells() + kHistCells - 1) / kHistCells), lat.n_rep);
+  const auto kernel = rep_int8 ? spgg_reputation_hist_kernel<true> : spgg_reputation_hist_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(kHistThreads), 0, s, lat.S0, lat.S1, R0, R1, params, lat.stop_iter, lat.L, t,
+                     bins, edges, out, (long long)out_stride);
 }
 
-void launch_pairs(const int8_t* R0, const int8_t* R1, const int32_t* stop_iter, int n_rep, int L, int t,
-                  int max_d, long long* out, int64_t out_stride, hipStream_t s) {
-  if (L > kMaxLdsSide) {
-    hipLaunchKernelGGL(spgg_reputation_pairs_global_kernel, dim3(2 * (max_d + 1), n_rep), dim3(kThreads), 0, s, R0, R1,
-                       stop_iter, L, t, max_d, out, (long long)out_stride);
-    return;
+void launch_pairs(const spgg_obs::Lattices& lat, const int8_t* R0, const int8_t* R1, int t, int max_d, long long* out,
+                  int64_t out_stride, hipStream_t s) {
+  dim3 grid((max_d + kDistPerGroup) / kDistPerGroup, lat.n_rep);
+  auto kernel = spgg_reputation_pairs_lds_kernel<kFullDwords>;
+  if (lat.L > kMaxLdsSide) {
+    kernel = spgg_reputation_pairs_global_kernel;
+    grid.x = 2 * (max_d + 1);
+  } else if (lattice_dwords(lat.L) <= kSmallDwords) {
+    kernel = spgg_reputation_pairs_lds_kernel<kSmallDwords>;
   }
-  const dim3 grid((max_d + kDistPerGroup) / kDistPerGroup, n_rep);
-  if (lattice_dwords(L) <= kSmallDwords)
-    hipLaunchKernelGGL(spgg_reputation_pairs_lds_kernel<kSmallDwords>, grid, dim3(kThreads), 0, s, R0, R1, stop_iter, L,
-                       t, max_d, out, (long long)out_stride);
-  else
-    hipLaunchKernelGGL(spgg_reputation_pairs_lds_kernel<kFullDwords>, grid, dim3(kThreads), 0, s, R0, R1, stop_iter, L,
-                       t, max_d, out, (long long)out_stride);
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, s, R0, R1, lat.stop_iter, lat.L, t, max_d, out,
+                     (long long)out_stride);
 }
 
 }  // namespace spgg_rp
