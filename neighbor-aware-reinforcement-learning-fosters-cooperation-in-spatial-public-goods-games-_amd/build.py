@@ -14,20 +14,24 @@ from concurrent.futures import ThreadPoolExecutor
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
-SRC = [os.path.join(PKG_DIR, "csrc", "spgg_kernels.hip"),
-       os.path.join(PKG_DIR, "csrc", "spgg_mt.hip"),   # MT19937 jump-ahead (its own object)
-       os.path.join(PKG_DIR, "csrc", "spgg_clusters.hip"),   # cluster labelling (its own object)
-       os.path.join(PKG_DIR, "csrc", "spgg_correlations.hip"),   # pair counts (its own object)
-       os.path.join(PKG_DIR, "csrc", "spgg_reputation.hip"),   # reputation record (its own object)
-       os.path.join(PKG_DIR, "csrc", "spgg_dwell.hip"),   # strategy dwell record (its own object)
-       os.path.join(PKG_DIR, "csrc", "spgg_clusters_tiled.hip")]   # cluster labelling over many workgroups (its own object)
+CSRC = os.path.join(PKG_DIR, "csrc")
+# The library's translation units: (source file, extra defines, object name), compiled in
+# parallel and linked into one shared library.  spgg_kernels.hip is one unit per RL operator
+# (SPGG_TU = the header's SPGG_ALG_* value: that operator's step kernels) and one for the
+# C ABI (SPGG_TU=9); every other source is one unit.
+UNITS = [(os.path.join(CSRC, "spgg_kernels.hip"), (f"SPGG_TU={k}",), f"tu{k}.o") for k in (0, 1, 2, 3, 9)]
+UNITS += [(os.path.join(CSRC, f"spgg_{name}.hip"), (), f"{name}.o")
+          for name in ("mt_gen",           # MT19937 draw generator
+                       "mt",               # MT19937 jump-ahead
+                       "clusters",         # cluster labelling
+                       "correlations",     # pair counts
+                       "reputation",       # reputation record
+                       "dwell",            # strategy dwell record
+                       "clusters_tiled")]  # cluster labelling over many workgroups
+SRC = list(dict.fromkeys(u[0] for u in UNITS))  # the distinct source files
 INC = os.path.join(ROOT, "include")
 OUT = os.path.join(PKG_DIR, "libspgg_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-# One translation unit per RL operator (its step kernels) + one for the C ABI,
-# compiled in parallel and linked into one shared library (spgg_kernels.hip's
-# SPGG_TU switch).
-TUS = (0, 1, 2, 3, 9)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          # bit-exact f64: no FMA contraction of the reference's a*b+c
          "-ffp-contract=off",
@@ -72,15 +76,13 @@ def build(force=False, verbose=True, out=OUT, defines=()):
         return out
     extra = [f"-D{d}" for d in defines] + [f'-DSPGG_BUILD_ID="{build_id(defines)}"']
     with tempfile.TemporaryDirectory() as tmp:
-        objs = [os.path.join(tmp, f"tu{k}.o") for k in TUS] + [os.path.join(tmp, "mt.o"), os.path.join(tmp, "clusters.o"),
-                                                                 os.path.join(tmp, "correlations.o"), os.path.join(tmp, "reputation.o"),
-                                                                 os.path.join(tmp, "dwell.o"), os.path.join(tmp, "clusters_tiled.o")]
-        cmds = [[HIPCC, *FLAGS, *extra, f"-DSPGG_TU={k}", f"-I{INC}", "-c", SRC[0], "-o", o]
-                for k, o in zip(TUS, objs)]
-        for src, o in zip(SRC[1:], objs[len(TUS):]):
-            cmds.append([HIPCC, *FLAGS, *extra, f"-I{INC}", "-c", src, "-o", o])
+        objs = [os.path.join(tmp, o) for _, _, o in UNITS]
+        cmds = [[HIPCC, *FLAGS, *extra, *(f"-D{d}" for d in defs), f"-I{INC}", "-c", src, "-o", o]
+                for (src, defs, _), o in zip(UNITS, objs)]
         if verbose:
-            print(" ".join(cmds[0]).replace("-DSPGG_TU=0", "-DSPGG_TU={0,1,2,3,9}"), flush=True)
+            for src, defs, o in UNITS:
+                print(f"{HIPCC} {' '.join(FLAGS)} {' '.join('-D' + d for d in defs)} -c {os.path.relpath(src, ROOT)} -> {o}",
+                      flush=True)
         jobs = max(1, min(len(cmds), os.cpu_count() or 1, int(os.environ.get("MAX_JOBS", "8"))))
         with ThreadPoolExecutor(jobs) as ex:
             for r in ex.map(lambda c: subprocess.run(c, capture_output=True, text=True), cmds):

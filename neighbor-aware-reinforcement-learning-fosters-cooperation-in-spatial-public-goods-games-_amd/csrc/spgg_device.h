@@ -5,6 +5,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "spgg_abi.h"
 
 namespace spgg {
@@ -22,6 +24,17 @@ __device__ __forceinline__ int wrap(int x, int L) {
   while (x < 0) x += L;
   while (x >= L) x -= L;
   return x;
+}
+
+// Element i of a per-replica array: scalar base + zero-extended 32-bit byte
+// offset, so every access is one global_load/store in saddr form with no
+// 64-bit address arithmetic (the host keeps each per-replica array < 4 GiB).
+// (char-pointer arithmetic, not an integer round trip: the compiler must still
+// see a global pointer, or it falls back to flat instructions.)
+template <typename T>
+__device__ __forceinline__ T* at(T* base, uint32_t i) {
+  using B = typename std::conditional<std::is_const<T>::value, const char, char>::type;
+  return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + (size_t)(i * (uint32_t)sizeof(T)));
 }
 
 // ---------------------------------------------------------------------------

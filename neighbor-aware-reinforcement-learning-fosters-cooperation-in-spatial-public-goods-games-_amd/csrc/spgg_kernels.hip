@@ -4,7 +4,7 @@
 // (src/model/spgg.py:368-592) covers every replica of the batch.  A
 // workgroup owns a TH x TW tile of one replica's periodic L x L lattice:
 //
-//   phase 0  stage S_t (halo M+2) and R_t (halo 2M) of the tile in LDS; load
+//   phase 0  stage S_t (halo M+2) and R_t (halo M) of the tile in LDS; load
 //            the owned agents' Q and pending neighbor-influence (NI) record
 //   phase 1  owned agents: apply the deferred NI term of iteration t-1
 //            (+ its Q statistics) -> payoff P (13-cell stencil) -> iteration
@@ -19,9 +19,11 @@
 // The NI term divides by a lattice-wide max (spgg.py:488), so it is applied
 // one launch later (or by spgg_flush) with the reference's exact arithmetic:
 //   Q[s,a] = (qc + alpha*td) + (kappa*max(0,md))/(gmax+lambda_eps) * (+-1).
-// Q and the pending max_diff are ping-ponged by iteration parity: a launch
-// reads only buffers the previous launch wrote, so the ring recompute never
-// races another workgroup's writes.
+// S, R and the border records are ping-ponged by iteration parity: a launch
+// reads only halves the previous launch wrote.  Q and the pending NI record
+// (max_diff, |alpha*td'|) are IN PLACE: an agent's entries are read and written
+// only by its owner, and the ring recompute reads the owner's border record of
+// iteration t-1 instead, so it never races another workgroup's writes.
 //
 // Every float op that feeds the simulation is f64 in the reference's
 // evaluation order; compiled with -ffp-contract=off (no FMA contraction).
@@ -43,6 +45,7 @@
 #include "spgg_abi.h"
 #include "spgg_test.h"
 #include "spgg_device.h"
+#include "spgg_draws.h"
 #include "spgg_mt.h"
 #include "spgg_clusters.h"
 #include "spgg_clusters_tiled.h"
@@ -51,42 +54,22 @@
 #include "spgg_dwell.h"
 
 using namespace spgg;
+using namespace spgg_gen;
 
-// Timing-only ablation builds (-DSPGG_ABLATE=mask; results are WRONG):
-//   1 = cheap hash instead of Philox, 2 = no history atomics, 4 = no ring recompute,
-//   8 = no history reductions (NCOOP kept constant), 64 = empty workgroups (launch floor),
-//   16 = no workgroup totals (final barrier + epilogue), 512 = no per-agent Q / md / atd loads
-//   (synthetic values), 2048 = no per-agent Q / md / atd stores, 8192 = no md loads / stores (the
-//   pending NI term reads +0), 16384 (with 8) = the lattice-wide max still recorded (the dynamics
-//   of the product), 32768 = no NI percent (its |alpha*td'| dead), 65536 = no phase-1b value
-//   reductions, 131072 = no counter reductions (NCOOP kept constant), 4096 = Q plane 0 read only (plane 1's
-//   entries copied from it), 128 = memory only (the owned loads,
-//   staging and stores, no compute)
-#ifndef SPGG_ABLATE
-#define SPGG_ABLATE 0
-#endif
-#ifndef SPGG_PRIO  // A/B probe: s_setprio of the load phase
-#define SPGG_PRIO 0
-#endif
-#ifndef SPGG_QNT  // A/B probe: bit 0 Q loads, bit 1 Q stores non-temporal (not for Double-Q)
-#define SPGG_QNT 0
-#endif
-#ifndef SPGG_QSTORE  // A/B probe: 0 changed rows, 1 both rows, 2 rows changed anywhere in the 8-agent line, 3 in the lane pair, 4 in the 8-lane group (DPP)
-#define SPGG_QSTORE 0
-#endif
-// (Rejected A/B knobs -- reward-code pending records, partial Q stores, non-temporal
-// per-agent streams, wave priorities -- live in profiles/r02/rejected_knobs.patch with
-// their measurements.)
+// The compile-time A/B probes the step kernel was measured with are kept out of this file, as
+// patches beside their measurements: profiles/probes/step_probes.patch (timing ablations by mask
+// -- which mask measured which floor is in its README --, wave priority of the load phase,
+// non-temporal and widened Q stores, the persistent path's timing variants) and
+// profiles/r02/rejected_knobs.patch (reward-code pending records, partial Q stores, non-temporal
+// per-agent streams).
 
-// Build layout: this file is compiled once per RL operator with
-// -DSPGG_TU=<SPGG_ALG_*> (that operator's step kernels only) and once with
-// -DSPGG_TU=9 (C ABI, MT19937 and payoff kernels); without SPGG_TU it is one
-// translation unit with everything.  The pieces meet in spgg_impl.
+// Build layout: this file is compiled once per RL operator with -DSPGG_TU=<SPGG_ALG_*> (that
+// operator's step kernels and their dispatch: the only unit that instantiates them) and once
+// with -DSPGG_TU=9 (the host: C ABI, history and payoff kernels).  The pieces meet in spgg_impl.
+// The MT19937 draw generator is spgg_mt_gen.hip, behind spgg_draws.h.
 #ifndef SPGG_TU
-#define SPGG_TU (-1)
+#error "spgg_kernels.hip is compiled per unit: -DSPGG_TU=<SPGG_ALG_*> or -DSPGG_TU=9 (build.py UNITS)"
 #endif
-#define SPGG_TU_HAS_ALG(k) (SPGG_TU == -1 || SPGG_TU == (k))
-#define SPGG_TU_HAS_HOST (SPGG_TU == -1 || SPGG_TU == 9)
 
 namespace spgg_impl {
 
@@ -148,7 +131,7 @@ struct PersistArgs {
 };
 constexpr int kBarWords = 16;
 
-// Enqueue one step-kernel launch of operator ALG (defined in that operator's TU): iteration t
+// Enqueue one step-kernel launch of operator ALG (defined and instantiated in that operator's unit): iteration t
 // (pa == nullptr), or the persistent launch of iterations t .. pa->t_end.
 template <int ALG>
 void launch_alg(const LaunchCfg& lc, const TileArgs& a, int t, int fin, hipStream_t s,
@@ -266,37 +249,17 @@ __host__ __device__ inline LdsLayout lds_layout(int tw, int th, int HS, int HA, 
   return l;
 }
 
-// Element i of a per-replica array: scalar base + zero-extended 32-bit byte
-// offset, so every access is one global_load/store in saddr form with no
-// 64-bit address arithmetic (the host keeps each per-replica array < 4 GiB).
-// (char-pointer arithmetic, not an integer round trip: the compiler must still
-// see a global pointer, or it falls back to flat instructions.)
-template <typename T>
-__device__ __forceinline__ T* at(T* base, uint32_t i) {
-  using B = typename std::conditional<std::is_const<T>::value, const char, char>::type;
-  return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + (size_t)(i * (uint32_t)sizeof(T)));
-}
-
 // A load / store of element p, plain or (SC1: inside a persistent launch, for bytes another
 // workgroup reads) write-through / past the CU's L1 -- relaxed agent-scope atomics, lowered to
 // global_load / global_store ... sc1 (the hand-off rules: replica_barrier below).
-#ifndef SPGG_PERSIST_PLAIN  // timing variant: plain hand-off accesses (results may be stale: WRONG)
-#define SPGG_PERSIST_PLAIN 0
-#endif
-#ifndef SPGG_PERSIST_STAGGER  // timing variant: s_sleep(16) x this per stagger rank after each barrier
-#define SPGG_PERSIST_STAGGER 0
-#endif
-#ifndef SPGG_PERSIST_NORECOMP  // timing variant: see step_impl's CARRY
-#define SPGG_PERSIST_NORECOMP 0
-#endif
 template <bool SC1, typename T>
 __device__ __forceinline__ T hload(const T* p) {
-  if constexpr (SC1 && !SPGG_PERSIST_PLAIN) return __hip_atomic_load(const_cast<T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (SC1) return __hip_atomic_load(const_cast<T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else return *p;
 }
 template <bool SC1, typename T>
 __device__ __forceinline__ void hstore(T* p, T v) {
-  if constexpr (SC1 && !SPGG_PERSIST_PLAIN) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (SC1) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else *p = v;
 }
 
@@ -670,11 +633,7 @@ template <int RNG>
 __device__ __forceinline__ void draw_pair(const TileArgs& a, int rep, int g, int t, uint32_t key, uint64_t thr,
                                           int k, int* ex, int* rbt) {
   if constexpr (RNG == SPGG_RNG_PHILOX) {
-#if SPGG_ABLATE & 1
-    *ex = ((g * 2654435761u + t + k) >> 7) % 50 == 0; *rbt = (g ^ t ^ k) & 1;
-#else
     philox_draw(g, t + (k << 26), key, thr, ex, rbt);
-#endif
   } else {
     *ex = draw_bit(a, rep, g, 2 * k);
     *rbt = draw_bit(a, rep, g, 2 * k + 1);
@@ -713,11 +672,7 @@ __device__ __forceinline__ void load_q(const double* Qr, uint32_t n, uint32_t ag
                                        double (&qb)[QB ? 4 : 1]) {
   const vd2* q0 = at(reinterpret_cast<const vd2*>(Qr), agent * (QB ? 2 : 1));
   const vd2* q1 = at(reinterpret_cast<const vd2*>(Qr), (n + agent) * (QB ? 2 : 1));
-#if SPGG_QNT & 1  // A/B probe: Q rows loaded non-temporally
-  const vd2 q01 = __builtin_nontemporal_load(q0), q23 = __builtin_nontemporal_load(q1);
-#else
-  const vd2 q01 = q0[0], q23 = (SPGG_ABLATE & 4096) ? q01 : q1[0];  // 4096: one plane's reads only
-#endif
+  const vd2 q01 = q0[0], q23 = q1[0];
   q[0] = q01.x; q[1] = q01.y; q[2] = q23.x; q[3] = q23.y;
   if constexpr (QB) {
     const vd2 b01 = q0[1], b23 = q1[1];
@@ -731,13 +686,6 @@ __device__ __forceinline__ void store_q(double* Qr, uint32_t n, uint32_t agent, 
                                         const double (&qb)[QB ? 4 : 1], uint32_t rows = 3u) {
   vd2* q0 = at(reinterpret_cast<vd2*>(Qr), agent * (QB ? 2 : 1));
   vd2* q1 = at(reinterpret_cast<vd2*>(Qr), (n + agent) * (QB ? 2 : 1));
-#if SPGG_QNT & 2  // A/B probe: Q rows stored non-temporally
-  if constexpr (!QB) {
-    if (rows & 1u) __builtin_nontemporal_store(vd2{q[0], q[1]}, q0);
-    if (rows & 2u) __builtin_nontemporal_store(vd2{q[2], q[3]}, q1);
-    return;
-  }
-#endif
   if (rows & 1u) {
     q0[0] = vd2{q[0], q[1]};
     if constexpr (QB) q0[1] = vd2{qb[0], qb[1]};
@@ -1076,10 +1024,10 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // it saves bound the launch (cfg3 65.5 -> 64.1 us/step in the driver's window, 54.2 -> 53.2
   // steady); the latency-bound small batches (two / one agent per thread) keep the stored record,
   // where the region pass's VALU sits on the critical path (cfg4 steady 12.2 -> 14.9 us/step)
-  constexpr bool RECOMP = ALG != ALG_SARSA && APT == spgg_impl::apt_of(ALG) && !(PERSIST && SPGG_PERSIST_NORECOMP);
+  constexpr bool RECOMP = ALG != ALG_SARSA && APT == spgg_impl::apt_of(ALG);
   // PERSIST: the stored pending record (md, atd) of the owned agents carried in registers from one
-  // iteration to the next (timing variant SPGG_PERSIST_NORECOMP: through global memory instead)
-  constexpr bool CARRY = PERSIST && !SPGG_PERSIST_NORECOMP;
+  // iteration to the next
+  constexpr bool CARRY = PERSIST;
   // both plus-count planes from the S window in one pass (build_plus_counts_both_dw); the
   // defector-bit plane is then neither staged nor read
   constexpr bool BOTH = RECOMP && TWC > 0;
@@ -1091,7 +1039,6 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   const int per_xcd = (total + 7) / 8;
   const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
   if (logical >= total) return;
-  if (SPGG_ABLATE & 64) return;
   const int lrep = logical / a0.tiles_per_rep;
   const int tile = logical - lrep * a0.tiles_per_rep;
   // the XCDs take consecutive tile ranges; a stride over the replicas spreads the cheap ones
@@ -1190,9 +1137,6 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   RT* Rout = reinterpret_cast<RT*>(a.R_out) + rb;
   const bool pending = t > 1;
   STAMP(0);
-#if SPGG_PRIO  // A/B probe: the load phase at a raised wave priority (back to 0 after staging)
-  if constexpr (!PERSIST) __builtin_amdgcn_s_setprio(SPGG_PRIO);
-#endif
 #if SPGG_STAMPS
   if (t == SPGG_STAMP_T && tid == 0 && stamp_id < kStampWG) {
     unsigned hw, xcc;
@@ -1225,15 +1169,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       // first one and drop it; md/atd are read even at t = 1, unused there):
       // conditional loads serialise on each other
       const uint32_t g = own ? g00 + __umul24((uint32_t)r, (uint32_t)L) + (uint32_t)c : g00 + (TWC ? (tid & 1) : 0);
-      if (SPGG_ABLATE & 512) {  // compute-floor probe: no per-agent loads
-#pragma unroll
-        for (int k = 0; k < 4; ++k) q[u][k] = (double)((g + k) & 15) * 1e-3;
-        if constexpr (QB) for (int k = 0; k < 4; ++k) qb[u][QB ? k : 0] = q[u][k];
-        md_own[u] = 0.0;
-        atd_own[u] = 0.f;
-      } else {
-        load_q<QB>(Qr, (uint32_t)n, g, q[u], qb[u]);
-      }
+      load_q<QB>(Qr, (uint32_t)n, g, q[u], qb[u]);
       r += dr;
       c += dc;
       if (c >= tw) {
@@ -1277,13 +1213,13 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // the pending NI record after every other load (its address waits for the replica's kappa): a
   // replica with kappa == 0 never uses it (phase 1a skips the NI term), so all its lanes read
   // the replica's first entry -- one cache line per wave instead of 12 B per agent
-  if (!(SPGG_ABLATE & 512) && !RECOMP && (first || !CARRY)) {
+  if (!RECOMP && (first || !CARRY)) {
     const bool ni_rec = __builtin_amdgcn_readfirstlane((int)(a.params[rep].kappa != 0.0)) != 0;
 #pragma unroll
     for (int u = 0; u < APT; ++u) {
       const uint32_t g = ni_rec ? agent_of(rc[u]) : 0u;
-      md_own[u] = (SPGG_ABLATE & 8192) ? 0.0 : *at(mdr, g);  // 8192: md traffic floor probe
-      atd_own[u] = (SPGG_ABLATE & 256) ? 0.f : *at(atdr, g);  // 256: atd traffic floor probe
+      md_own[u] = *at(mdr, g);
+      atd_own[u] = *at(atdr, g);
     }
   }
   // draw-record words of the region rows (DSTAGE): row ry, slot sl: 32-agent group
@@ -1395,23 +1331,6 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   }
   __syncthreads();
   STAMP(1);
-#if SPGG_PRIO
-  if constexpr (!PERSIST) __builtin_amdgcn_s_setprio(0);
-#endif
-  if (SPGG_ABLATE & 128) {  // memory floor: write back what was read
-#pragma unroll
-    for (int u = 0; u < APT; ++u) {
-      const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
-      store_q<QB>(Qr, (uint32_t)n, agent_of(rc[u]), q[u], qb[u]);
-      if (!RECOMP) {
-        *at(mdr, agent_of(rc[u])) = md_own[u];
-        *at(atdr, agent_of(rc[u])) = atd_own[u];
-      }
-      *at(Sout, agent_of(rc[u])) = sSv[(r + HS) * ly.sw + (c + HS)];
-      if (!AS) *at(Rout, agent_of(rc[u])) = sRv[(r + HA) * ly.aw + (c + HA)];
-    }
-    return;
-  }
   // plus counts for the payoffs of phases 1b / 1c (their barrier: after phase 1a) and, for the
   // recomputed NI record, of iteration t-1 (BOTH: one pass builds the two planes)
   const bool rec_prev = RECOMP && pending && kappa != 0.0;  // workgroup-uniform
@@ -1534,7 +1453,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
           // NI percent (spgg.py:512; x100 applied to the workgroup total), in f32:
           // a history mean (tolerance 1e-5), each term a ratio in [0, 1]
           const float anu = fabsf((float)nu);
-          pct = (SPGG_ABLATE & 32768) ? 0.f : __builtin_fmaf(anu * __builtin_amdgcn_rcpf((atdv + anu) + 1e-8f), (float)vmu, pct);
+          pct = __builtin_fmaf(anu * __builtin_amdgcn_rcpf((atdv + anu) + 1e-8f), (float)vmu, pct);
         }
         const double cm = ((b >> 3) & 1) ? 0.0 : vmu;                  // prev_S of t-1 == C
 #pragma unroll
@@ -1581,7 +1500,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // lane computes the blocks of slots j < APT/2, the odd lane those of j + APT/2, and
   // each hands the partner its half (one DPP swap): half the Philox work per agent
   // (the blocks of slots 2j and 2j+1 are made just before slot 2j: two bit words live, not APT)
-  constexpr bool PAIRED = RNG == SPGG_RNG_PHILOX && TWC > 0 && APT % 2 == 0 && !(SPGG_ABLATE & 1);
+  constexpr bool PAIRED = RNG == SPGG_RNG_PHILOX && TWC > 0 && APT % 2 == 0;
   uint32_t pbits[APT];
   {
     double va[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1641,7 +1560,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     va[0] = (double)rsum;
     va[3] = (double)pct_t1;
     // red[wave*64 + 16..19]: va[0..3] (reduced here: frees their registers for phases 1c / 2)
-    if (!(SPGG_ABLATE & (8 | 65536))) wave_partials<4>(va, red, 16, tid);
+    wave_partials<4>(va, red, 16, tid);
   }
   STAMP(3);
 
@@ -1649,7 +1568,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // Their Q row of state s_t (S_t bit 4) and max_diff come from the owner's
   // border record of iteration t-1; the owner applies the same NI term to
   // the same entry, so both agree bit for bit.
-  if (acting && !(SPGG_ABLATE & 4)) {
+  if (acting) {
 #pragma unroll
     for (int j = 0; j < RP; ++j) {
       const int k = tid + j * kBlock;
@@ -1722,25 +1641,10 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       const float atd = td_update<ALG, RNG>(a, hp, rep, agent_of(rc[u]), t, pkey, eps_t, eps53, diag_on, rew, so,
                                             act, sn, q[u], qb[u], &rn0, &rn1);
       if constexpr (CARRY) atd_own[u] = atd;  // (carried to the next iteration's phase 1a)
-      else if (diag_on && !(SPGG_ABLATE & (256 | 2048))) *at(atdr, agent_of(rc[u])) = atd;  // read only for the NI percent (0 when kappa == 0)
+      else if (diag_on) *at(atdr, agent_of(rc[u])) = atd;  // read only for the NI percent (0 when kappa == 0)
       // the rows this launch changed: the TD row (so) and the NI row of t-1 (phase 1a)
-      if (!PERSIST && !(SPGG_ABLATE & 2048)) {
-        uint32_t rows = ((ni_rows >> (2 * u)) & 3u) | (1u << so);
-#if SPGG_QSTORE == 1
-        rows = 3u;
-#elif SPGG_QSTORE == 2
-        rows |= (uint32_t)__shfl_xor((int)rows, 1);
-        rows |= (uint32_t)__shfl_xor((int)rows, 2);
-        rows |= (uint32_t)__shfl_xor((int)rows, 4);
-#elif SPGG_QSTORE == 3
-        if constexpr (TWC > 0 && TWC % 2 == 0) rows |= partner<1>(rows);
-#elif SPGG_QSTORE == 4
-        if constexpr (TWC > 0 && TWC % 8 == 0) {
-          rows |= partner<1>(rows);
-          rows |= partner<2>(rows);
-          rows |= partner<4>(rows);
-        }
-#endif
+      if (!PERSIST) {
+        const uint32_t rows = ((ni_rows >> (2 * u)) & 3u) | (1u << so);
         store_q<QB>(Qr, (uint32_t)n, agent_of(rc[u]), q[u], qb[u], rows);
       }
       // neighbour influence, spgg.py:477-494: first argmax wins ties
@@ -1775,7 +1679,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       // max(0, max_diff) feeds only the next launch's NI term, which is +0 when kappa == 0
       // (phase 1a and the ring skip it): not stored then (-8 B/agent-step for those replicas)
       if constexpr (CARRY) md_own[u] = mdp;
-      else if (ni_on && !RECOMP && !(SPGG_ABLATE & (2048 | 8192))) *at(mdr, agent_of(rc[u])) = mdp;
+      else if (ni_on && !RECOMP) *at(mdr, agent_of(rc[u])) = mdp;
       hstore<PERSIST>(at(Sout, agent_of(rc[u])), (uint8_t)((rc[u] & 0xff) | (dp << 2) | (sn << 4)));
       hstore<PERSIST>(at(Rout, agent_of(rc[u])), (RT)sRn[ca]);
       const int bslot = (int)(int16_t)(uint16_t)(bsw >> (16 * u));  // (table: border_slot_table)
@@ -1799,7 +1703,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     }
   }
   STAMP(5);
-  if (!(SPGG_ABLATE & (8 | 131072))) {  // red[wave*64 + 24..29]: counter words (fields of the layout above)
+  {  // red[wave*64 + 24..29]: counter words (fields of the layout above)
     uint32_t cw[8] = {cw0,
                       cw1,
                       nmd2 | ((gcn & 0xfu) << 16),
@@ -1814,24 +1718,11 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     const double wm = wave_max(bmax);
     if ((tid & 63) == 0) red[(tid >> 6) * 64 + 12] = wm;
   }
-  if (SPGG_ABLATE & 16) {  // timing probe: no workgroup totals (barrier + epilogue); NCOOP kept constant
-    if (tid == 0 && tile == 0 && acting) srow[(size_t)(t + 1) * SPGG_NSTAT] = n / 2;
-    return;
-  }
   __syncthreads();
   STAMP(6);
 
   // ---- workgroup totals -> per-iteration history record ------------------
-  if ((SPGG_ABLATE & (8 | 131072)) && tid == 0 && tile == 0 && acting) srow[(size_t)(t + 1) * SPGG_NSTAT] = n / 2;
-  if ((SPGG_ABLATE & 16392) == 16392 && tid == 40 && acting) {  // 8 + 16384: the lattice max kept (dynamics unchanged)
-    double bm = 0.0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) bm = max_f64(bm, red[w * 64 + 12]);
-    if (bm > 0.0)
-      atomicMax(reinterpret_cast<unsigned long long*>(&srow[(size_t)t * SPGG_NSTAT + SPGG_ST_GMAX]),
-                (unsigned long long)__double_as_longlong(bm));
-  }
-  if (tid < 64 && !(SPGG_ABLATE & 8)) {
+  if (tid < 64) {
     // lane -> record value: source word src of every wave's red[] (and, for derived values, its
     // "C" partner src_c); lane 40 reads the wave maxima (word 12) for the lattice-wide max
     int slot = -1, k = -1, src = 12, src_c = -1;
@@ -1860,7 +1751,6 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       const bool start_val = j == 0;                   // recorded on the absorbing iteration too
       if ((acting || start_val) && k >= 0) slot = (j == 5) ? t + 1 : t;
     }
-    if ((SPGG_ABLATE & 131072) && tid >= 19 && tid <= 29) slot = -1;  // (counter fields)
     // every word of the four waves read at once, unconditionally: one LDS round trip (the reads
     // chained under the derived values' branches held the workgroup's last wave, and with it the
     // CU's slot for the next workgroup, ~0.9 us)
@@ -1893,8 +1783,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       if (counter) val = (double)(((unsigned long long)tot0 >> (16 * ((j - 3) & 1))) & 0xffffu);
       if (RQ && k == SPGG_ST_SUMR) val *= rep_unit;
       if (k == SPGG_ST_SUM_PCT || k == SPGG_ST_SUM_RATIO_C) val *= 100.0;  // percent sums
-      if (val != 0.0 && (!(SPGG_ABLATE & 2) || k == SPGG_ST_NCOOP))
-        atomicAdd(&srow[(size_t)slot * SPGG_NSTAT + k], val);
+      if (val != 0.0) atomicAdd(&srow[(size_t)slot * SPGG_NSTAT + k], val);
     }
   }
   STAMP(7);
@@ -1911,9 +1800,6 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       break;
     }
     STAMP(11);
-#if SPGG_PERSIST_STAGGER  // timing variant: workgroups start the next iteration staggered by (blockIdx/8)%4
-    for (int z = 0; z < ((blockIdx.x >> 3) & 3) * SPGG_PERSIST_STAGGER; ++z) __builtin_amdgcn_s_sleep(16);
-#endif
   }
   }  // iterations
   if constexpr (PERSIST) {
@@ -2079,12 +1965,10 @@ void launch_t(const LaunchCfg& lc, const TileArgs& a, int t, int fin, hipStream_
       return;
     }
   }
-#ifndef SPGG_NO_TWC
   if (lc.twc == 40)  // the tile every L that is a multiple of 40 gets (L = 200, 1000)
     hipLaunchKernelGGL((spgg_step_kernel<M2, AS, RQ, RNG, APT, 40, ALG>), grid, dim3(kBlock), lc.lds_bytes, s, a,
                        t, fin);
   else
-#endif
     hipLaunchKernelGGL((spgg_step_kernel<M2, AS, RQ, RNG, APT, 0, ALG>), grid, dim3(kBlock), lc.lds_bytes, s, a,
                        t, fin);
 }
@@ -2127,488 +2011,36 @@ void launch_alg(const LaunchCfg& lc, const TileArgs& a, int t, int fin, hipStrea
   }
 }
 
-// Explicit instantiation in the operator's own translation unit; elsewhere
-// an extern declaration keeps the kernels from being instantiated again.
-#define SPGG_LAUNCH_INST(k, name)                                                                   \
-  template void launch_alg<name>(const LaunchCfg&, const TileArgs&, int, int, hipStream_t, const PersistArgs*); \
-  template int persist_blocks_per_cu<name>(const LaunchCfg&);
-#define SPGG_LAUNCH_EXTERN(k, name)                                                                 \
-  extern template void launch_alg<name>(const LaunchCfg&, const TileArgs&, int, int, hipStream_t,   \
-                                        const PersistArgs*);                                        \
-  extern template int persist_blocks_per_cu<name>(const LaunchCfg&);
-#if SPGG_TU_HAS_ALG(0)
-#if SPGG_STAMPS
+// Every unit declares the four operators' instances extern, so that none instantiates another's
+// kernels; an operator's own unit then instantiates its own.
+extern template void launch_alg<SPGG_ALG_QLEARNING>(const LaunchCfg&, const TileArgs&, int, int, hipStream_t, const PersistArgs*);
+extern template void launch_alg<SPGG_ALG_SARSA>(const LaunchCfg&, const TileArgs&, int, int, hipStream_t, const PersistArgs*);
+extern template void launch_alg<SPGG_ALG_EXPECTED_SARSA>(const LaunchCfg&, const TileArgs&, int, int, hipStream_t, const PersistArgs*);
+extern template void launch_alg<SPGG_ALG_DOUBLE_Q>(const LaunchCfg&, const TileArgs&, int, int, hipStream_t, const PersistArgs*);
+extern template int persist_blocks_per_cu<SPGG_ALG_QLEARNING>(const LaunchCfg&);
+extern template int persist_blocks_per_cu<SPGG_ALG_SARSA>(const LaunchCfg&);
+extern template int persist_blocks_per_cu<SPGG_ALG_EXPECTED_SARSA>(const LaunchCfg&);
+extern template int persist_blocks_per_cu<SPGG_ALG_DOUBLE_Q>(const LaunchCfg&);
+#if SPGG_TU != 9
+template void launch_alg<SPGG_TU>(const LaunchCfg&, const TileArgs&, int, int, hipStream_t, const PersistArgs*);
+template int persist_blocks_per_cu<SPGG_TU>(const LaunchCfg&);
+#endif
+
 }  // namespace spgg_impl
+
+#if SPGG_STAMPS && SPGG_TU == SPGG_ALG_QLEARNING
 extern "C" int spgg_stamps_read(void* dst, size_t bytes) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(spgg_stamps), bytes < sizeof(spgg_stamps) ? bytes : sizeof(spgg_stamps));
 }
-namespace spgg_impl {
-#endif
-SPGG_LAUNCH_INST(0, SPGG_ALG_QLEARNING)
-#else
-SPGG_LAUNCH_EXTERN(0, SPGG_ALG_QLEARNING)
-#endif
-#if SPGG_TU_HAS_ALG(1)
-SPGG_LAUNCH_INST(1, SPGG_ALG_SARSA)
-#else
-SPGG_LAUNCH_EXTERN(1, SPGG_ALG_SARSA)
-#endif
-#if SPGG_TU_HAS_ALG(2)
-SPGG_LAUNCH_INST(2, SPGG_ALG_EXPECTED_SARSA)
-#else
-SPGG_LAUNCH_EXTERN(2, SPGG_ALG_EXPECTED_SARSA)
-#endif
-#if SPGG_TU_HAS_ALG(3)
-SPGG_LAUNCH_INST(3, SPGG_ALG_DOUBLE_Q)
-#else
-SPGG_LAUNCH_EXTERN(3, SPGG_ALG_DOUBLE_Q)
 #endif
 
-}  // namespace spgg_impl
-
-#if SPGG_TU_HAS_HOST
+#if SPGG_TU == 9  // the host unit
 namespace {
-
-// ---------------------------------------------------------------------------
-// Device MT19937, bit-identical to numpy.random.RandomState (legacy seeding,
-// randomkit mt19937_gen + tempering), generating the draw records of whole
-// chunks of iterations ahead of the step kernels (spgg_step runs it on its own
-// stream; the draws depend on nothing but the key and the eps schedule).
-//
-// The raw word stream obeys x[k+624] = x[k+397] ^ twist(x[k], x[k+1]), so the 227
-// words of a block [F, F+227) depend only on words >= 227 back: block-parallel.
-// One workgroup per chain, no barrier after the prologue:
-//   wave 0, the recurrence: the 227 positions of a block in 4 slots of lanes
-//     (gen_slot_base), x[F+j] from x[F+j-227] (the lane's previous word of the slot, a
-//     register) and x[F+j-624], x[F+j-623] (the LDS ring, 2-3 blocks old; read one block
-//     ahead).  It publishes its completed blocks (gen_done) every kGenPub blocks; one
-//     wave's LDS operations complete in order.  The ring holds kGenNB blocks at fixed positions (block b at 256*(b % kGenNB),
-//     + a mirror of block 0 behind the last one), so with the block loop unrolled kGenNB
-//     times every LDS address is a lane constant plus an immediate offset, and no LDS
-//     operation of the recurrence sits under a branch;
-//   the other kGenOut waves: temper + threshold + pack the finished words (below the
-//     frontier 624 + 227*min(gen_done)): 64 draws per wave instruction, one __ballot, two
-//     32-bit stores -- the draw record holds one BIT per draw (spgg_abi.h).  They publish
-//     the first word they still need (gen_need), which the recurrence must not overwrite.
-// Per executed iteration the reference draws rand(L,L) (2 words per double,
-// algorithms.py:105) then randint(0,2,(L,L)) (1 word each, algorithms.py:108);
-// SARSA twice more (spgg.py:434, 452), Double-Q then rand(L,L) < 0.5
-// (algorithms.py:307).  After each iteration the key (the 624-word block holding
-// the last consumed word, + pos) is saved to a snapshot ring, from which
-// spgg_flush restores the key the reference would hold (spgg_mt_final_kernel).
-__device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
-}
-
-using spgg_mt::mt_next;
-
-// bit 0 of mt_temper(y) as a function of y: y0 ^ y3 ^ y14 ^ y18 ^ y22 ^ y29 (the tempering
-// shifts and masks of mt_temper composed; tests/test_mt_jump_cpu.py checks it on numpy)
-constexpr uint32_t kTemperBit0 = 0x20444009u;
-
-// Draw program of one iteration, in the reference's order: plane i is rand(L,L)
-// compared with a threshold (2 words per value, i even) or randint(0,2,(L,L))
-// (1 word, i odd).
-//   Q-learning / Expected SARSA: D(eps) I            (algorithms.py:105,108)
-//   SARSA:   D(eps) I D(eps) I D(eps) I              (+ spgg.py:434, 452)
-//   Double-Q: D(eps) I D(0.5)                        (+ algorithms.py:307)
-__host__ __device__ inline int draw_planes(int alg) {
-  return alg == SPGG_ALG_SARSA ? 6 : alg == SPGG_ALG_DOUBLE_Q ? 3 : 2;
-}
-// MT words one iteration consumes, and the first word of plane p within them.
-__host__ __device__ inline int64_t draw_mt_words(int64_t n, int planes) { return n * (planes / 2 * 3 + (planes & 1) * 2); }
-__host__ __device__ inline uint32_t plane_word0(uint32_t n, int p) { return n * (uint32_t)(p / 2 * 3 + (p & 1) * 2); }
-// u32 words of one replica's draw record: 64-draw chunks (two words each) x planes.
-__host__ __device__ inline int64_t draw_words_of(int n, int alg) {
-  return (int64_t)((n + 63) / 64) * 2 * draw_planes(alg);
-}
-
-// One recurrence wave and three output waves per chain: the A/B variants of this layout
-// (2 recurrence waves, 1-3 output waves, publication periods, wave priorities, VGPR caps,
-// timing ablations) were measured in round 3 and live in profiles/r03/rejected_gen_knobs.patch.
-#ifndef SPGG_GEN_OUT
-#define SPGG_GEN_OUT 3
-#endif
-constexpr int kGenOut = SPGG_GEN_OUT;            // output waves
-constexpr int kGenSPW = 4;                       // slots of the lone recurrence wave
-// Blocks between two progress publications of the recurrence wave (each publication waits
-// for the wave's LDS writes: one exposed LDS round trip per period).
-constexpr int kGenPub = 4;
-
-// Chunks an output wave handles per batch (one wait, one need publication, one store of the
-// batch's draw words; the ring coordinates stepped, not divided, from one chunk to the next).
-constexpr int kGenU = 4;
-constexpr int kGenThreads = 64 * (1 + kGenOut);
-constexpr int kMtBlock = 227;                    // 624 - 397: words one dependency step produces
-// Ring words per block: none of padding, so a chunk's words are contiguous across a block
-// boundary (and into the mirror of block 0 past the last block): one lane address per read.
-constexpr int kGenPitch = kMtBlock;
-// Ring blocks.  Not a lever: 8 or 12 (10 / 14 KB of LDS instead of 18) measured the same whole runs
-// (profiles/r04/generator_groups.txt) -- with the generator resident, the step kernel's occupancy
-// is bound by VGPRs, not LDS.
-#ifndef SPGG_GEN_NB
-#define SPGG_GEN_NB 16
-#endif
-constexpr int kGenNB = SPGG_GEN_NB;
-static_assert(kGenNB == 16 || kGenNB == 8, "the block loop is unrolled kGenNB times");
-static_assert(kGenNB % kGenPub == 0, "publication period divides the unrolled block loop");
-// an output wave reads at most kGenU x kGenOut x 128 - 1 words past its published need (a batch);
-// the frontier it is guaranteed to see lies (kGenNB - kGenPub) x 227 + 1 words past the smallest need
-static_assert(kGenU * kGenOut * 128 - 1 < (kGenNB - kGenPub) * kMtBlock + 1, "output waves' progress");
-constexpr int kGenRingWords = kGenPitch * kGenNB;
-constexpr int kGenRing = kGenRingWords + kGenPitch;  // + a mirror of block 0 behind the last one
-// Progress a failed recurrence wave publishes: every output wave's wait then ends at once.
-constexpr uint32_t kGenDoneAbort = (0xffffffffu - 624u) / kMtBlock;
-// Bound of every wait loop between the generator's waves (0.2-0.5 s of s_sleep): a wait that
-// long means a defect.  The wave then records SPGG_GEN_ERR_SPIN in the context's error word,
-// which spgg_flush / spgg_status report (SPGG_E_STATE: the draws of such a run are not the
-// reference's), releases the other waves (need 0xffffffff / progress kGenDoneAbort) and
-// stops, so the kernel ends instead of hanging the GPU.  (The recurrence wave stops through its
-// last-block path: an early return there took the kernel from 51 to 74 VGPRs.)
-constexpr uint32_t kGenSpinMax = 1u << 23;
-#ifndef SPGG_GEN_SLEEP_OUT  // s_sleep argument of a polling output wave (x 64 clocks)
-#define SPGG_GEN_SLEEP_OUT 1
-#endif
-#ifndef SPGG_GEN_SLEEP_REC  // s_sleep argument of the recurrence wave waiting for the output waves
-#define SPGG_GEN_SLEEP_REC 2
-#endif
-
-// The 227 positions of a block in 4 slots of 64 lanes: slot s holds positions
-// base(s) + lane for lane < len(s).  Positions 169-226 need positions 0-57 of the block two
-// back (every other position only blocks three back), so slots 0 and 1 -- the same wave --
-// hold both: a wave reads another wave's words only from blocks >= 2 behind, which leaves
-// each wave a block of slack.  The lanes past len(s) (29 = 256 - 227 of them) DUPLICATE lane
-// (lane - len(s)) of their slot -- the same position, operands and previous word, so they compute
-// and write the same value to the same address -- so every LDS write is unconditional and the
-// ring has no padding.
-__host__ __device__ constexpr int gen_slot_base(int s) { return s == 0 ? 0 : s == 1 ? 169 : s == 2 ? 58 : 122; }
-__host__ __device__ constexpr int gen_slot_len(int s) { return s == 0 ? 58 : s == 1 ? 58 : s == 2 ? 64 : 47; }
-__device__ __forceinline__ int gen_position(int s, int lane) {
-  return gen_slot_base(s) + (lane < gen_slot_len(s) ? lane : lane - gen_slot_len(s));
-}
-
-struct GenArgs {
-  const uint32_t* key_in;  // [rep][625] chain 0's key + pos: mt_state, or the chunk's key buffer
-  uint32_t* key_out;       // [rep][625] the key after the launch's last iteration (its last chain)
-  const uint32_t* parts;   // chains >= 1: start windows, [rep][chain][kSplits][624] XOR parts
-  const uint32_t* run_pos0;  // [rep] first word of the run's iteration 1 in its key block
-  int chains, per_chain;   // chain c: iterations t0 + c*per_chain .. (+ per_chain - 1)
-  uint32_t* snap;          // snapshot slot s of replica rep: snap + s*snap_stride + rep*625
-  int64_t snap_stride;
-  int snap_slots;
-  uint32_t* draws;         // draw record of iteration t: draws + ((t-1) % draw_slots)*draw_stride
-  int64_t draw_stride;
-  int draw_slots;
-  int draw_words;          // per replica (draw_words_of)
-  const double* eps;       // [rep][eps_slots]
-  int eps_slots;
-  const int* stop_iter;
-  uint32_t* err;           // the context's error word (SPGG_GEN_ERR_*), OR-ed on a failed wait
-  int n, alg;
-};
-
-// A wait between the generator's waves ran out of its bound: recorded for the host (one lane,
-// a vector global atomic).
-__device__ __forceinline__ void gen_fail(const GenArgs& g) {
-  if ((threadIdx.x & 63) == 0) atomicOr(g.err, (uint32_t)SPGG_GEN_ERR_SPIN);
-}
-
-// Flags shared through LDS between the generator's waves: relaxed workgroup-scope atomics
-// on the __shared__ array itself (plain ds_read / ds_write; through a generic pointer they
-// become flat accesses with system-scope waits).  Every lane of a wave writes its own copy
-// (no branch around the store); readers read lane 0's.  A flag store is a release: it waits
-// until every earlier LDS access of the wave has completed (lgkmcnt(0); issue order alone
-// does not order another wave's view of two writes), and the compiler may not move an
-// access across it; a reader only touches the ring after its flag read returned.
-#define LDS_LD(x) __hip_atomic_load(&(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-// after a wait on a flag: no memory access of the wave may be moved above the wait by the
-// compiler (relaxed atomics do not order the plain ring accesses; the hardware does)
-#define GEN_FENCE() asm volatile("" ::: "memory")
-#define LDS_ST(x, v)                                                          \
-  do {                                                                        \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                        \
-    __hip_atomic_store(&(x), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-  } while (0)
-
-// Word k of a launch (the key block = words 0..623) lives in ring block (k + 57) / 227 - 3
-// (mod kGenNB), at offset (k + 57) % 227: blocks b >= 0 hold words 624 + 227 b ..
-// (blocks are contiguous, so that is ring position (k - 624) mod kGenRingWords)
-__device__ __forceinline__ uint32_t gen_word_pos(uint32_t k) {
-  static_assert(kGenPitch == kMtBlock, "contiguous ring blocks");
-  return (k + (uint32_t)(kGenRingWords - 624)) % (uint32_t)kGenRingWords;
-}
-
-// Iterations t0..t1 of every replica, from its key; writes the draw records, the key
-// snapshots (slot t % snap_slots = the key after iteration t; t0 == 1 also slot 0 = the
-// initial key) and the advanced key.  blockIdx.x = rep * chains + c: chain c runs
-// iterations t0 + c*per_chain .. (+ per_chain - 1) from its window -- chain 0 from key_in
-// (an aligned key block + pos), chain c >= 1 from the XOR of its parts: the window that
-// starts at its first draw word, whose offset within the reference's 624-word key blocks
-// is ph.  Word indices are relative to the chain's window (the host keeps a chain below
-// 2^31 words).  skip_stopped: replicas already absorbed are left alone (their draws are
-// never read).
-__global__ __launch_bounds__(kGenThreads) void spgg_mt_gen_kernel(GenArgs g, int t0, int t1, int skip_stopped) {
-  __shared__ uint32_t ring[kGenRing];
-  __shared__ uint32_t gen_done[64];           // blocks the recurrence wave has published (per lane)
-  __shared__ uint32_t gen_need[kGenOut][64];  // output wave w reads no word below this (per lane)
-  __shared__ uint32_t pos_sh;
-  const int rep = blockIdx.x / g.chains, ch = blockIdx.x - rep * g.chains, tid = threadIdx.x;
-  bool last_chain;  // the chain whose iterations end the launch: it writes key_out
-  {
-    const int ct0 = t0 + ch * g.per_chain;
-    if (ct0 > t1) return;
-    last_chain = ct0 + g.per_chain - 1 >= t1;
-    t1 = min(t1, ct0 + g.per_chain - 1);
-    t0 = ct0;
-  }
-  if (skip_stopped && g.stop_iter[rep] != 0) return;
-  const int planes = draw_planes(g.alg);
-  const uint32_t W = (uint32_t)draw_mt_words(g.n, planes);
-  uint32_t ph = 0;  // offset of the window's first word within a key block
-  if (ch == 0) {
-    const uint32_t* key = g.key_in + (size_t)rep * 625;
-    for (int i = tid; i < 624; i += kGenThreads) ring[gen_word_pos(i)] = key[i];
-    if (tid == 0) pos_sh = key[624];  // next word to consume (624: the block is exhausted)
-    if (t0 == 1) {
-      uint32_t* s0 = g.snap + (size_t)rep * 625;
-      for (int i = tid; i < 625; i += kGenThreads) s0[i] = key[i];
-    }
-  } else {
-    const uint32_t* pp = g.parts + (size_t)(rep * g.chains + ch) * spgg_mt::kSplits * 624;
-    for (int i = tid; i < 624; i += kGenThreads) {
-      uint32_t v = 0;
-#pragma unroll
-      for (int p = 0; p < spgg_mt::kSplits; ++p) v ^= pp[p * 624 + i];
-      ring[gen_word_pos(i)] = v;
-    }
-    if (tid == 0) pos_sh = 0;
-    ph = (uint32_t)(((uint64_t)g.run_pos0[rep] + (uint64_t)(t0 - 1) * W) % 624u);
-  }
-  if (tid < 64) gen_done[tid] = 0;
-  if (tid < 64 * kGenOut) gen_need[tid >> 6][tid & 63] = 0;
-  __syncthreads();
-  const uint32_t pos0 = pos_sh;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  // first word of the key block holding word E - 1 (window-relative; >= 0: W >= 624 for chains)
-  auto key_block = [ph](uint32_t E) { return ((E - 1 + ph) / 624) * 624 - ph; };
-  // blocks of 227 words this launch generates: through the key block of its last iteration
-  uint32_t nblk;
-  {
-    const uint32_t E_last = pos0 + (uint32_t)(t1 - t0 + 1) * W;
-    const uint32_t target_last = key_block(E_last) + 624;
-    nblk = target_last > 624 ? (target_last - 624 + kMtBlock - 1) / kMtBlock : 0;
-  }
-  if (wave == 0) {
-    // ---- the recurrence: every slot of every block ------------------------------------------
-    __builtin_amdgcn_s_setprio(3);  // the critical path
-    uint32_t prev[kGenSPW], ca[kGenSPW], cb[kGenSPW];
-    uint32_t *wp[kGenSPW], *pa[kGenSPW], *pb[kGenSPW];  // lane addresses: own word, its two operands
-#pragma unroll
-    for (int i = 0; i < kGenSPW; ++i) {
-      const int j = gen_position(i, lane);
-      wp[i] = ring + j;
-      pa[i] = ring + j + 57;  // (a word past 227 is the next block's: contiguous ring)
-      pb[i] = ring + j + 58;
-      prev[i] = wp[i][(kGenNB - 1) * kGenPitch];  // x[397 + j]: block -1
-      ca[i] = pa[i][(kGenNB - 3) * kGenPitch];    // operands of block 0: block -3
-      cb[i] = pb[i][(kGenNB - 3) * kGenPitch];
-    }
-    uint32_t E = pos0 + W;
-    uint32_t mb = key_block(E), target = mb + 624;
-    uint32_t lim = 0;   // largest F whose block may be written (output waves' reads)
-    int t = t0;
-    uint32_t key_mb = 0, key_pos = pos0;
-    uint32_t b = 0;     // blocks completed
-    bool aborted = false;  // a flow-control wait ran out of its bound
-    // key after iteration t (words [mb, mb+624) and pos), to the snapshot ring; then the next
-    auto retire = [&]() {
-      uint32_t* sn = g.snap + (size_t)(t % g.snap_slots) * g.snap_stride + (size_t)rep * 625;
-#pragma unroll 1
-      for (int m = 0; m < 10; ++m) {
-        const uint32_t i = lane + 64 * m;
-        if (i < 624) sn[i] = ring[gen_word_pos(mb + i)];
-      }
-      if (lane == 0) sn[624] = E - mb;
-      key_mb = mb;
-      key_pos = E - mb;
-      ++t;
-      E += W;
-      mb = key_block(E);
-      target = mb + 624;
-    };
-    // one block: b % kGenNB == U; operands ca/cb were read one block ahead
-#define SPGG_GEN_BLOCK(U)                                                                                 \
-  {                                                                                                       \
-    if (b == nblk) goto rec_done;                                                                         \
-    while (t <= t1 && 624u + kMtBlock * b >= target) retire();                                            \
-    const uint32_t F = 624u + kMtBlock * b;                                                               \
-    uint32_t spin = 0;                                                                                    \
-    for (; F > lim && spin < kGenSpinMax; ++spin) { /* flow control: no output wave still reads the     \
-                                                       positions written */                               \
-      uint32_t m = 0xffffffffu;                                                                           \
-      _Pragma("unroll") for (int w = 0; w < kGenOut; ++w) m = min(m, LDS_LD(gen_need[w][0]));             \
-      m = __builtin_amdgcn_readfirstlane(m);                                                              \
-      /* (saturating: finished output waves publish 0xffffffff) */                                       \
-      lim = m > 0xffffffffu - (kGenNB - 1) * kMtBlock ? 0xffffffffu : m + (kGenNB - 1) * kMtBlock;        \
-      if (F > lim) __builtin_amdgcn_s_sleep(SPGG_GEN_SLEEP_REC);                                          \
-    }                                                                                                     \
-    if (F > lim) { /* the bound ran out (the condition, not the counter: a last poll that succeeds    \
-                      is no failure); this block is the last: rec_done publishes kGenDoneAbort */       \
-      gen_fail(g);                                                                                        \
-      aborted = true;                                                                                     \
-      nblk = b + 1;                                                                                       \
-    }                                                                                                     \
-    GEN_FENCE();                                                                                          \
-    uint32_t na[kGenSPW], nb[kGenSPW];                                                                    \
-    _Pragma("unroll") for (int i = 0; i < kGenSPW; ++i) {                                                 \
-      constexpr int rb = ((U + 1 + kGenNB - 3) % kGenNB) * kGenPitch;                                     \
-      na[i] = pa[i][rb];                                                                                  \
-      nb[i] = pb[i][rb];                                                                                  \
-    }                                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < kGenSPW; ++i) {                                                 \
-      const uint32_t x = mt_next(prev[i], ca[i], cb[i]);                                                  \
-      prev[i] = x;                                                                                        \
-      wp[i][U * kGenPitch] = x;                                                                           \
-      if (U == 0) wp[i][kGenNB * kGenPitch] = x; /* mirror of block 0 */                                  \
-      ca[i] = na[i];                                                                                      \
-      cb[i] = nb[i];                                                                                      \
-    }                                                                                                     \
-    ++b;                                                                                                  \
-    if ((U + 1) % kGenPub == 0) LDS_ST(gen_done[lane], b);                                                \
-  }
-    for (;;) {
-      SPGG_GEN_BLOCK(0) SPGG_GEN_BLOCK(1) SPGG_GEN_BLOCK(2) SPGG_GEN_BLOCK(3)
-      SPGG_GEN_BLOCK(4) SPGG_GEN_BLOCK(5) SPGG_GEN_BLOCK(6) SPGG_GEN_BLOCK(7)
-#if SPGG_GEN_NB == 16
-      SPGG_GEN_BLOCK(8) SPGG_GEN_BLOCK(9) SPGG_GEN_BLOCK(10) SPGG_GEN_BLOCK(11)
-      SPGG_GEN_BLOCK(12) SPGG_GEN_BLOCK(13) SPGG_GEN_BLOCK(14) SPGG_GEN_BLOCK(15)
-#endif
-    }
-#undef SPGG_GEN_BLOCK
-  rec_done:
-    LDS_ST(gen_done[lane], aborted ? kGenDoneAbort : b);  // (published every kGenPub blocks: the rest)
-    GEN_FENCE();
-    while (t <= t1) retire();  // (the frontier covers every remaining target)
-    if (last_chain) {
-      uint32_t* key = g.key_out + (size_t)rep * 625;
-      for (int i = lane; i < 624; i += 64) key[i] = ring[gen_word_pos(key_mb + i)];
-      if (lane == 0) key[624] = key_pos;
-    }
-    return;
-  }
-  // ---- output waves: chunks ow, ow + kGenOut, ... of every plane of every iteration --------
-  // (per chunk: one ring read per lane, the temper / parity, one ballot; per batch of kGenU
-  // chunks: one wait, the batch's first word published as the wave's need, one store)
-  const int ow = wave - 1;
-  const uint64_t thr_half = u53_threshold(0.5);
-  const int nchunk = (g.n + 63) / 64;
-  uint32_t kpos = pos0;
-  uint32_t seen = 624;  // the frontier as last read
-  // lane 2u + h of a batch's store: half h of the draw word of the batch's chunk u
-  // (the record's word of chunk c, plane p, half h: 2 c planes + h planes + p, spgg_abi.h)
-  const uint32_t lane_off = (uint32_t)(((lane >> 1) * kGenOut * 2 + (lane & 1)) * planes);
-  // the draws of the plane's last chunk (n % 64 of them when partial)
-  const uint64_t tail = (g.n & 63) ? (1ull << (g.n & 63)) - 1ull : ~0ull;
-  for (int t = t0; t <= t1; ++t) {
-    const uint64_t thr = u53_threshold(g.eps[(size_t)rep * g.eps_slots + t]);
-    uint32_t* rec_out = g.draws + (size_t)((t - 1) % g.draw_slots) * g.draw_stride + (size_t)rep * g.draw_words;
-    for (int p = 0; p < planes; ++p) {
-      const bool dbl = (p & 1) == 0;
-      // rand() < th: ((a>>5) * 2^26 + (b>>6)) / 2^53 < th as a 53-bit integer compare, decided
-      // by a alone unless its 27 bits equal th's (p = 2^-27: b is read only then)
-      const uint64_t th = (g.alg == SPGG_ALG_DOUBLE_Q && p == 2) ? thr_half : thr;
-      const uint32_t th_hi = __builtin_amdgcn_readfirstlane((uint32_t)(th >> 26));
-      const uint32_t th_lo = __builtin_amdgcn_readfirstlane((uint32_t)th & ((1u << 26) - 1u));
-      const uint32_t base = kpos + plane_word0((uint32_t)g.n, p);
-      // (the chunk loop is instantiated per plane kind: the kind's branches leave the loop)
-      auto chunks = [&](auto dbl_c) -> bool {
-        constexpr bool dbl = decltype(dbl_c)::value;
-        constexpr uint32_t wmul = dbl ? 2u : 1u;           // words per draw
-        constexpr uint32_t cstep = 64u * wmul * kGenOut;    // words from one chunk of this wave to its next
-        static_assert(cstep * kGenU < (uint32_t)kGenRingWords, "a batch stays within one turn of the ring");
-        const uint32_t wlane = wmul * (uint32_t)lane;
-        // the current chunk's first word and its ring position, stepped per chunk: word k sits at
-        // (k - 624) mod kGenRingWords (gen_word_pos; the blocks are contiguous)
-        uint32_t first = base + 64u * wmul * (uint32_t)ow;
-        uint32_t rpos = gen_word_pos(first);
-        for (int c = ow; c < nchunk; c += kGenOut * kGenU) {
-          const int nb = min(kGenU, (nchunk - 1 - c) / kGenOut + 1);  // chunks of this batch
-          const int cl = c + (nb - 1) * kGenOut;
-          const uint32_t last = first + cstep * (uint32_t)(nb - 1) + wmul * (uint32_t)min(64, g.n - 64 * cl) - 1u;
-          LDS_ST(gen_need[ow][lane], first);
-          if (seen <= last) {  // wait for the recurrence (the check of its bound only on this path)
-            uint32_t spin = 0;
-            for (; seen <= last && spin < kGenSpinMax; ++spin) {
-              seen = 624u + kMtBlock * __builtin_amdgcn_readfirstlane(LDS_LD(gen_done[0]));
-              if (seen <= last) __builtin_amdgcn_s_sleep(SPGG_GEN_SLEEP_OUT);
-            }
-            if (seen <= last) {  // (the condition itself: a last poll that succeeds is no failure)
-              gen_fail(g);
-              LDS_ST(gen_need[ow][lane], 0xffffffffu);
-              return false;
-            }
-          }
-          GEN_FENCE();
-          // the batch's words first (one LDS round trip; a chunk past the batch reads a ring word
-          // it drops), then per chunk: the chunk's <= 128 words are contiguous from its ring position
-          // (past the last block: the mirror of block 0)
-          uint32_t rp[kGenU], x[kGenU];
-#pragma unroll
-          for (int u = 0; u < kGenU; ++u) {
-            rp[u] = u == 0 ? rpos : rp[u - 1] + cstep;
-            if (u > 0) rp[u] -= rp[u] >= (uint32_t)kGenRingWords ? (uint32_t)kGenRingWords : 0u;
-            x[u] = ring[rp[u] + wlane];
-          }
-          uint32_t val = 0;
-#pragma unroll
-          for (int u = 0; u < kGenU; ++u) {
-            if (u < nb) {
-              bool flag;
-              if (dbl) {
-                const uint32_t ah = mt_temper(x[u]) >> 5;
-                flag = ah < th_hi;
-                if (ah == th_hi) flag = (mt_temper(ring[rp[u] + wlane + 1]) >> 6) < th_lo;
-              } else {  // randint(0, 2) = the tempered word's low bit = parity of raw bits 0,3,14,18,22,29
-                flag = (__builtin_popcount(x[u] & kTemperBit0) & 1) != 0;
-              }
-              // (lanes past n read stale words: masked)
-              const uint64_t bits = __builtin_amdgcn_ballot_w64(flag) & (c + u * kGenOut == nchunk - 1 ? tail : ~0ull);
-              val = lane == 2 * u ? (uint32_t)bits : lane == 2 * u + 1 ? (uint32_t)(bits >> 32) : val;
-            }
-          }
-          rpos += cstep * (uint32_t)nb;
-          rpos -= rpos >= (uint32_t)kGenRingWords ? (uint32_t)kGenRingWords : 0u;
-          if (lane < 2 * nb) *at(rec_out, (uint32_t)(2 * c * planes + p) + lane_off) = val;
-          first += cstep * (uint32_t)nb;
-        }
-        return true;
-      };
-      if (!(dbl ? chunks(std::true_type{}) : chunks(std::false_type{}))) return;
-    }
-    kpos += W;
-  }
-  LDS_ST(gen_need[ow][lane], 0xffffffffu);  // done: never blocks the recurrence
-}
 
 // spgg_test_set_error: ORs flags into a context's generator error word, on the generator's
 // stream, as a failing wait does (tests of the error path).
 __global__ void spgg_set_err_kernel(uint32_t* err, uint32_t flags) {
   if (threadIdx.x == 0) atomicOr(err, flags);
-}
-
-// spgg_flush (MT19937): the key the reference holds after the run -- after the last
-// iteration a replica executed (its absorbing iteration draws nothing) -- from the ring.
-__global__ void spgg_mt_final_kernel(GenArgs g, int t_last) {
-  const int rep = blockIdx.x;
-  const int st = g.stop_iter[rep];
-  const int src = st ? st - 1 : t_last;
-  const uint32_t* sn = g.snap + (size_t)(src % g.snap_slots) * g.snap_stride + (size_t)rep * 625;
-  uint32_t* key = g.key_out + (size_t)rep * 625;
-  for (int i = threadIdx.x; i < 625; i += blockDim.x) key[i] = sn[i];
 }
 
 // History values derived from device counts (spgg_history_finalize), for iterations
@@ -3141,8 +2573,7 @@ GenArgs gen_args(const spgg_ctx* c, int q = -1) {
 
 void launch_gen(const spgg_ctx* c, int t0, int t1, int skip_stopped, hipStream_t s, int q = -1) {
   const GenArgs g = gen_args(c, q);
-  hipLaunchKernelGGL(spgg_mt_gen_kernel, dim3(c->cfg.n_rep * g.chains), dim3(kGenThreads), 0, s, g, t0, t1,
-                     skip_stopped);
+  spgg_gen::launch_gen(g, t0, t1, skip_stopped, c->cfg.n_rep * g.chains, s);
 }
 
 // A stream for the library's generator (gen) or the caller's replica groups (spgg_stream_create).
@@ -3636,7 +3067,7 @@ int spgg_flush(spgg_ctx* c, int32_t t_last, void* stream) {
       return fail(c, SPGG_E_STATE, "spgg_flush: the MT19937 draw generator failed (error word " +
                                        std::to_string(*c->h_err) + "): a wait between its waves ran out of "
                                        "its bound, so this run's draws are not the reference's");
-    hipLaunchKernelGGL(spgg_mt_final_kernel, dim3(c->cfg.n_rep), dim3(256), 0, s, gen_args(c), t_last);
+    spgg_gen::launch_final(gen_args(c), t_last, c->cfg.n_rep, s);
   }
   launch_step(c, t_last + 1, 1, s);
   return hip_check(c, hipGetLastError(), "spgg_flush launch");
@@ -3908,4 +3339,4 @@ int spgg_destroy(spgg_ctx* c) {
 }
 
 }  // extern "C"
-#endif  // SPGG_TU_HAS_HOST
+#endif  // SPGG_TU == 9

@@ -1,4 +1,4 @@
-// spgg_mt.h — MT19937 jump-ahead for the device draw generator (spgg_kernels.hip).
+// spgg_mt.h — MT19937 jump-ahead for the device draw generator (spgg_mt_gen.hip).
 //
 // A replica's draws are one MT19937 stream (numpy RandomState, the reference's global RNG:
 // src/model/algorithms.py:105,108, spgg.py:434,452).  Its recurrence is serial per stream, so

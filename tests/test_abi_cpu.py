@@ -141,3 +141,21 @@ def test_tuning_knobs_need_the_tuning_switch(monkeypatch):
     assert lib.spgg_tile_shape(ctx, ctypes.byref(tw), ctypes.byref(th)) == _lib.OK
     assert (tw.value, th.value) != (16, 16)
     lib.spgg_destroy(ctx)
+
+
+def test_build_table_covers_every_source():
+    """Every csrc/*.hip is the source of at least one unit of build.py's table (a new file cannot
+    be left out of the link), and the step kernels are one unit per operator, carrying the header's
+    four SPGG_ALG_* values."""
+    import glob
+    from spgg_amd import build as B
+    sources = sorted(glob.glob(os.path.join(B.PKG_DIR, "csrc", "*.hip")))
+    assert sources and set(sources) == {src for src, _, _ in B.UNITS} == set(B.SRC)
+    assert len({obj for _, _, obj in B.UNITS}) == len(B.UNITS)          # no object overwrites another
+    algs = {int(v) for v in re.findall(r"#define SPGG_ALG_\w+ (\d+)", open(HEADER).read())}
+    assert len(algs) == 4
+    # the source compiled more than once: one unit per operator, told apart by one define's value
+    srcs = [src for src, _, _ in B.UNITS]
+    multi = [defs for src, defs, _ in B.UNITS if srcs.count(src) > 1]
+    assert all(len(defs) == 1 for defs in multi) and len(set(multi)) == len(multi)
+    assert algs <= {int(defs[0].split("=")[1]) for defs in multi}

@@ -1,4 +1,4 @@
-"""A model check of the MT19937 draw generator's wave protocol (csrc/spgg_kernels.hip,
+"""A model check of the MT19937 draw generator's wave protocol (csrc/spgg_mt_gen.hip,
 spgg_mt_gen_kernel) on the CPU: the recurrence and output waves are restated as coroutines
 that yield at every LDS access, run under random interleavings over a sequentially
 consistent LDS, and their outputs are compared with numpy's RandomState stream.

@@ -103,7 +103,7 @@ def test_powers_compose():
 
 def test_tempered_low_bit_is_a_parity_of_raw_bits():
     """randint(0, 2) is the tempered word's bit 0; the generator computes it as the parity of
-    raw bits 0, 3, 14, 18, 22, 29 (spgg_kernels.hip kTemperBit0)."""
+    raw bits 0, 3, 14, 18, 22, 29 (spgg_mt_gen.hip kTemperBit0)."""
     y = np.random.RandomState(0).randint(0, 2 ** 32, size=200_000, dtype=np.uint32)
     z = y & np.uint32(0x20444009)
     par = np.zeros_like(z)

@@ -5,7 +5,7 @@ barrier segment and per source function.
                                  [--asm file.s] [--keep file.s]
 
 Rebuilds one translation unit of csrc/spgg_kernels.hip to gfx950 assembly with the build's own
-compiler and flags (spgg_amd.build: HIPCC, FLAGS, -DSPGG_TU=<tu>) plus -gline-tables-only (line
+compiler and flags (spgg_amd.build: HIPCC, FLAGS, the defines of that unit in UNITS) plus -gline-tables-only (line
 directives only: the code is the build's), or reads --asm.  The instance is
 spgg_step_kernel<M2, AS, RQ, RNG, APT, TWC, ALG>; the default is the one bench.py's cfg3 runs.
 
@@ -48,8 +48,9 @@ def mangled(instance):
 def assemble(tu, keep):
     import spgg_amd.build as B
     out = keep or os.path.join(tempfile.mkdtemp(prefix="ledger"), f"tu{tu}.s")
-    cmd = [B.HIPCC, *B.FLAGS, '-DSPGG_BUILD_ID="ledger"', f"-DSPGG_TU={tu}", f"-I{B.INC}", "-gline-tables-only",
-           "--cuda-device-only", "-S", B.SRC[0], "-o", out]
+    src, defs, _ = next(u for u in B.UNITS if f"SPGG_TU={tu}" in u[1])  # the unit of the build table
+    cmd = [B.HIPCC, *B.FLAGS, '-DSPGG_BUILD_ID="ledger"', *(f"-D{d}" for d in defs), f"-I{B.INC}", "-gline-tables-only",
+           "--cuda-device-only", "-S", src, "-o", out]
     subprocess.run(cmd, check=True)
     return out
 
