@@ -209,7 +209,7 @@ namespace {
 
 
 struct LdsLayout {
-  int sw, sh, aw, ah;
+  int sw, sh, aw, ah, pcp;  // pcp: pitch of the plus-count planes
   int off_Rew, off_R, off_Rn, off_S, off_D, off_A, off_PC, off_DR, off_DP, bytes;
 };
 
@@ -218,12 +218,16 @@ struct LdsLayout {
 // 3 from column 0 (the cells past the periodic wrap) -- and, repacked, the row's 64 region cells.
 constexpr int kDrawSlots = 6;
 
-// Pitch of the plus-count plane: one 64-lane wave row per region row.
+// Pitch of the plus-count plane of run-time-width tiles: one 64-lane wave row per region row.
+// Compile-time-width tiles give it the dword-aligned pitch of their other planes (it holds
+// region + 1 ring, two columns less than the S window), so that a region cell has ONE index
+// into every plane (step_impl, "slot word").
 constexpr int kPcPitch = 64;
 
 // 16-byte aligned carve: f64 first, then the R planes (rsz = 8 or 1), then bytes.
 // S and defector-bit planes: tile + halo HS (payoffs over tile + HA); the
-// plus-count plane: tile + HA + 1 rows of kPcPitch; everything else tile + HA.
+// plus-count plane: tile + HA + 1 rows of pcp (kPcPitch, or the common pitch of dword_rows);
+// everything else tile + HA.
 // dword_rows (compile-time-width kernels): every plane has one dword-aligned
 // pitch wide enough for a window staged as aligned dwords (window column j at
 // plane column j + its 0..3-byte misalignment).
@@ -233,6 +237,7 @@ __host__ __device__ inline LdsLayout lds_layout(int tw, int th, int HS, int HA, 
   l.sw = tw + 2 * HS; l.sh = th + 2 * HS;
   l.aw = tw + 2 * HA; l.ah = th + 2 * HA;
   if (dword_rows) l.sw = l.aw = (tw + 2 * HS + 3 + 3) / 4 * 4;
+  l.pcp = dword_rows ? l.aw : kPcPitch;
   const int na = l.aw * l.ah;
   int off = (12 + kWaves * 64) * 8;  // payoff table + reduction scratch
   l.off_Rew = off;  off += ((na * 8 + 15) / 16) * 16;
@@ -241,7 +246,7 @@ __host__ __device__ inline LdsLayout lds_layout(int tw, int th, int HS, int HA, 
   l.off_S = off;    off += ((l.sw * l.sh + 15) / 16) * 16;
   l.off_D = off;    off += ((l.sw * l.sh + kPcPitch + 15) / 16) * 16;  // + slack: full-wave row reads
   l.off_A = off;    off += ((na + 15) / 16) * 16;
-  l.off_PC = off;   off += (l.ah + 2) * kPcPitch;
+  l.off_PC = off;   off += (l.ah + 2) * l.pcp;
   off = (off + 15) / 16 * 16;
   l.off_DR = off;   off += draws ? l.ah * kDrawSlots * 2 * 4 : 0;
   l.off_DP = off;   off += draws ? l.ah * 2 * 2 * 4 : 0;
@@ -497,8 +502,9 @@ __device__ __forceinline__ void build_plus_counts(uint8_t* pc, const uint8_t* d,
 // as aligned dwords and the five neighbour bytes of four consecutive cells are funnel
 // shifts of two of them (v_alignbit).  Each byte sum is <= 5 and x8 <= 40, so no byte
 // carries into the next; bytes past the window (uninitialised) feed only higher, unused
-// bytes.  DWPR = dwords per plane row (>= the region width + 2, / 4).
-template <int DWPR>
+// bytes.  DWPR = dwords per plane row (>= the region width + 2, / 4); PCP = the plane's pitch in
+// bytes (a multiple of 4, >= 4 DWPR).
+template <int DWPR, int PCP>
 __device__ __forceinline__ void build_plus_counts_dw(uint8_t* pc, const uint8_t* dplane, int sw, int rows,
                                                      int soff, int tid) {
   const uint32_t s0 = 8u * soff, s1 = s0 + 8u, s2 = s0 + 16u;
@@ -512,7 +518,7 @@ __device__ __forceinline__ void build_plus_counts_dw(uint8_t* pc, const uint8_t*
     const uint32_t cnt = __builtin_amdgcn_alignbit(a1, a0, s1) + __builtin_amdgcn_alignbit(b1, b0, s0) +
                          __builtin_amdgcn_alignbit(b1, b0, s1) + __builtin_amdgcn_alignbit(b1, b0, s2) +
                          __builtin_amdgcn_alignbit(c1, c0, s1);
-    *reinterpret_cast<uint32_t*>(pc + y * kPcPitch + xd * 4) = cnt << 3;
+    *reinterpret_cast<uint32_t*>(pc + y * PCP + xd * 4) = cnt << 3;
   }
 }
 
@@ -534,7 +540,7 @@ __device__ __forceinline__ void build_plus_counts_prev(uint8_t* pc, const uint8_
 // defector count of S_t in bits 0-2 and that of S_{t-1}, already x8, in bits 3-5 (<= 5 + 40: no
 // byte carries into the next).  pc gets the first x8, pp (when `prev`: workgroup-uniform) the
 // second; one set of LDS reads and funnel shifts instead of two, and no defector-bit plane.
-template <int DWPR>
+template <int DWPR, int PCP>
 __device__ __forceinline__ void build_plus_counts_both_dw(uint8_t* pc, uint8_t* pp, const uint8_t* splane, int sw,
                                                           int rows, int soff, bool prev, int tid) {
   const uint32_t s0 = 8u * soff, s1 = s0 + 8u, s2 = s0 + 16u;
@@ -549,22 +555,24 @@ __device__ __forceinline__ void build_plus_counts_both_dw(uint8_t* pc, uint8_t* 
     const uint32_t cnt = __builtin_amdgcn_alignbit(a1, a0, s1) + __builtin_amdgcn_alignbit(b1, b0, s0) +
                          __builtin_amdgcn_alignbit(b1, b0, s1) + __builtin_amdgcn_alignbit(b1, b0, s2) +
                          __builtin_amdgcn_alignbit(c1, c0, s1);
-    *reinterpret_cast<uint32_t*>(pc + y * kPcPitch + xd * 4) = (cnt & 0x07070707u) << 3;
-    if (prev) *reinterpret_cast<uint32_t*>(pp + y * kPcPitch + xd * 4) = cnt & 0x38383838u;
+    *reinterpret_cast<uint32_t*>(pc + y * PCP + xd * 4) = (cnt & 0x07070707u) << 3;
+    if (prev) *reinterpret_cast<uint32_t*>(pp + y * PCP + xd * 4) = cnt & 0x38383838u;
   }
 }
 
-// Payoff of the region cell (ry, rx) (spgg.py:230-259, 373-377): the five
+// Payoff of the region cell (ry, rx) of a plus-count plane of pitch PCP (spgg.py:230-259,
+// 373-377; a caller that holds the cell's index ry * PCP + rx passes it as rx with ry = 0): the five
 // group defector counts are plus counts at the cell and its four axial
 // neighbours, each a byte offset into tb = the table of the cell's own
 // strategy indexed by defector count; summed in the reference's group order,
 // normalised.
 #define T_AT(t, o) (*reinterpret_cast<const double*>((t) + (o)))
+template <int PCP>
 __device__ __forceinline__ double payoff_pc(const uint8_t* pc, int ry, int rx, const double* tb, double norm_min,
                                             double norm_den, double norm_rcp) {
-  const uint8_t* p = pc + ry * kPcPitch + rx + 1;  // plus count of N0[i-1, j]
+  const uint8_t* p = pc + ry * PCP + rx + 1;  // plus count of N0[i-1, j]
   const char* t = reinterpret_cast<const char*>(tb);
-  const uint32_t x0 = p[kPcPitch], x1 = p[0], x2 = p[2 * kPcPitch], x3 = p[kPcPitch - 1], x4 = p[kPcPitch + 1];
+  const uint32_t x0 = p[PCP], x1 = p[0], x2 = p[2 * PCP], x3 = p[PCP - 1], x4 = p[PCP + 1];
   double tot = T_AT(t, x0);                   // group (0,0)  -> N0[i,j]
   tot = tot + T_AT(t, x1);                     // group (1,0)  -> N0[i-1,j]
   tot = tot + T_AT(t, x2);                     // group (-1,0) -> N0[i+1,j]
@@ -1031,6 +1039,20 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // both plus-count planes from the S window in one pass (build_plus_counts_both_dw); the
   // defector-bit plane is then neither staged nor read
   constexpr bool BOTH = RECOMP && TWC > 0;
+  // draw bits staged through LDS (one load round trip with the windows) instead of a record
+  // load per agent at the point of use (MT19937 steps 8 us slower than Philox before this)
+  constexpr bool DSTAGE = RNG != SPGG_RNG_PHILOX && TWC > 0;
+  // compile-time-width tiles: every plane, the plus-count planes included, has the pitch PITCH
+  // (lds_layout, dword_rows), so region cell (ry, rx) is ry * PITCH + rx in all of them
+  constexpr int PITCH = TWC ? (TWC + 2 * HS + 3 + 3) / 4 * 4 : 0;
+  constexpr int PCP = TWC ? PITCH : kPcPitch;
+  static_assert(TWC == 0 || (TWC + 2 * HA + 2 + 3) / 4 * 4 <= PITCH, "a plus-count row fits the common pitch");
+  // slot word by region index (below): the per-launch large-batch kernels (the operator's most
+  // agents per thread) whose draws need no (row, column) -- the staged draw bits are addressed by
+  // row and column; a persistent launch re-derives the agent index from the slot word each
+  // iteration, which takes the row; the latency-bound two-per-thread kernels lose a wave of
+  // occupancy to the held agent indices; the second-order kernels run at four waves already
+  constexpr bool SLOT = !M2 && TWC > 0 && !DSTAGE && !PERSIST && APT == spgg_impl::apt_of(ALG) && ALG != ALG_DQ;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   // XCD-aware placement: blocks b, b+8, b+16... share an XCD (round-robin
@@ -1057,9 +1079,6 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   const int th = min(a0.TH, L - y0), tw = TWC ? TWC : min(a0.TW, L - x0);
   // LDS pitches from the full tile width (constants when TWC > 0); edge tiles
   // use the top-left part of each region
-  // draw bits staged through LDS (one load round trip with the windows) instead of a record
-  // load per agent at the point of use (MT19937 steps 8 us slower than Philox before this)
-  constexpr bool DSTAGE = RNG != SPGG_RNG_PHILOX && TWC > 0;
   const LdsLayout ly = TWC ? lds_layout(TWC, a0.TH, HS, HA, (int)sizeof(RT), true, DSTAGE)
                            : lds_layout(tw, th, HS, HA, (int)sizeof(RT));
   double* tab = reinterpret_cast<double*>(smem);
@@ -1091,9 +1110,14 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // bit-identical to the owner's); only its history contributions are masked
   // (vm = 0).  Per-slot branches cost more in exec-mask and copy instructions.
   // slot u: (r << 16) | (c << 8) | its action bits (a | s_old << 1 | dp << 2 | s_t << 3 | s' << 4, set
-  // from phase 1b on); the agent index is agent_of(rc[u]) (recomputed, not held)
+  // from phase 1b on); the agent index is AGENT_U(u) (recomputed, not held)
+  // SLOT: (idx << 8) | the same bits, idx = r * PITCH + c the agent's tile-local index at the
+  // planes' common pitch: every plane address of a phase is idx plus a workgroup-uniform origin
+  // (plane, halo and misalignment: one scalar, or the access's immediate offset), and the agent
+  // index is held per slot in gi[u] (made once, with the slot word)
   // (PERSIST: q, qb, md_own, atd_own and the slots carry over from one iteration to the next)
   int rc[APT];
+  uint32_t gi[SLOT ? APT : 1];  // (unused without SLOT)
   unsigned vbits = 0;  // bit u: slot u holds an owned agent
   // Slots u < NFULL hold an owned agent in every thread of every tile (width-40 tiles of the
   // operator's most agents per thread: the host's twc_of admits them only where the smallest
@@ -1110,6 +1134,14 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   const uint32_t g00 = (uint32_t)(y0 * L + x0);
   // (row < 256, L < 2^24: a full-rate 24-bit multiply instead of the quarter-rate 32-bit one)
   auto agent_of = [&](int rcu) { return g00 + __umul24((uint32_t)(rcu >> 16), (uint32_t)L) + ((rcu >> 8) & 0xff); };
+  // the agent index of slot u (an expression, not a lambda over the arrays: the kernels that keep
+  // the (row, column) word then compile as they did)
+#define AGENT_U(u) (SLOT ? gi[SLOT ? (u) : 0] : agent_of(rc[u]))
+  // region (tile + ring) and S-window cell of a slot word
+  // (SLOT only; the (row, column) word keeps the expressions it always had, written out where they
+  // are used: the allocation of the kernels that keep it follows their text closely)
+  auto ca_of = [&](int rcu) -> int { return (int)((uint32_t)rcu >> 8) + (HA * PITCH + HA); };
+  auto cs_of = [&](int rcu) -> int { return (int)((uint32_t)rcu >> 8) + (HS * PITCH + HS); };
   bool stored = false;  // PERSIST: the table is in memory (absorbing iteration, or a failed wait)
   int t = t0;
   for (;; ++t) {
@@ -1163,12 +1195,19 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       const bool own = u < NFULL || k < n_own;
       // (TWC tiles: odd lanes shadow the tile's second agent, so lane pairs keep holding
       // agent pairs (2m, 2m+1) -- the Philox blocks of phase 1b are shared per lane pair)
-      rc[u] = own ? (r << 16) | (c << 8) : (TWC ? (tid & 1) << 8 : 0);
+      if constexpr (SLOT) rc[u] = (own ? r * PITCH + c : (tid & 1)) << 8;
+      else rc[u] = own ? (r << 16) | (c << 8) : (TWC ? (tid & 1) << 8 : 0);
       vbits |= own ? 1u << u : 0u;
       // loads unconditional (threads without a u-th agent read the tile's
       // first one and drop it; md/atd are read even at t = 1, unused there):
       // conditional loads serialise on each other
       const uint32_t g = own ? g00 + __umul24((uint32_t)r, (uint32_t)L) + (uint32_t)c : g00 + (TWC ? (tid & 1) : 0);
+      if constexpr (SLOT) {
+        // (opaque: as the plain copy of g, the index's multiples that address the Q loads here
+        // were kept for the stores of phase 2 -- 18 VGPRs across every phase, and the fifth wave)
+        gi[u] = g;
+        asm("" : "+v"(gi[u]));
+      }
       load_q<QB>(Qr, (uint32_t)n, g, q[u], qb[u]);
       r += dr;
       c += dc;
@@ -1217,7 +1256,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     const bool ni_rec = __builtin_amdgcn_readfirstlane((int)(a.params[rep].kappa != 0.0)) != 0;
 #pragma unroll
     for (int u = 0; u < APT; ++u) {
-      const uint32_t g = ni_rec ? agent_of(rc[u]) : 0u;
+      const uint32_t g = ni_rec ? AGENT_U(u) : 0u;
       md_own[u] = *at(mdr, g);
       atd_own[u] = *at(atdr, g);
     }
@@ -1336,9 +1375,9 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   const bool rec_prev = RECOMP && pending && kappa != 0.0;  // workgroup-uniform
   if constexpr (BOTH) {
     if (!fin_only || rec_prev)
-      build_plus_counts_both_dw<(TWC + 2 * HA + 2 + 3) / 4>(sPC, sPP, sS, ly.sw, ah + 2, soffS, rec_prev, tid);
+      build_plus_counts_both_dw<(TWC + 2 * HA + 2 + 3) / 4, PCP>(sPC, sPP, sS, ly.sw, ah + 2, soffS, rec_prev, tid);
   } else if (!fin_only) {
-    if constexpr (TWC > 0) build_plus_counts_dw<(TWC + 2 * HA + 2 + 3) / 4>(sPC, sD, ly.sw, ah + 2, soffS, tid);
+    if constexpr (TWC > 0) build_plus_counts_dw<(TWC + 2 * HA + 2 + 3) / 4, PCP>(sPC, sD, ly.sw, ah + 2, soffS, tid);
     else build_plus_counts(sPC, sDv, ly.sw, ah + 2, tid);
   }
   // the rewards of iteration t-1 over the region (tile + ring), into sRew (phase 1a reads them;
@@ -1350,7 +1389,8 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     int ry = tid / aw, rx = tid - (tid / aw) * aw;
     for (int k = tid; k < aw * ah; k += kBlock) {
       const uint8_t b = sSv[(ry + (HS - HA)) * ly.sw + (rx + (HS - HA))];
-      const double P = payoff_pc(sPP, ry, rx, tab + (((b >> 3) & 1) ? 6 : 0), hp.norm_min, hp.norm_den, hp.norm_rcp);
+      const double P = payoff_pc<PCP>(sPP, ry, rx, tab + (((b >> 3) & 1) ? 6 : 0), hp.norm_min, hp.norm_den,
+                                      hp.norm_rcp);
       const double rr = (b & 1) ? 0.0 : 0.5;                    // a_{t-1} = S_t (spgg.py:424-427)
       const double wpp = w_p * P, wrr = w_rep * rr;
       sRew[ry * ly.aw + rx] = wpp + wrr;
@@ -1404,8 +1444,12 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     uint8_t sb[APT];  // S_t bytes of the owned agents: s_t (bit 0) and the state (bit 4) go to rc
 #pragma unroll
     for (int u = 0; u < APT; ++u) {
-      const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
-      sb[u] = sSv[(r + HS) * ly.sw + (c + HS)];
+      if constexpr (SLOT) {
+        sb[u] = sSv[cs_of(rc[u])];
+      } else {
+        const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
+        sb[u] = sSv[(r + HS) * ly.sw + (c + HS)];
+      }
       rc[u] |= (AS ? 0 : ((sb[u] >> 4) & 1) << 1) | ((sb[u] & 1) << 3);
     }
     if (pending) {
@@ -1421,8 +1465,13 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
           double mdp, qe = 0.0;
           float atdv;
           if constexpr (RECOMP) {  // the record of t-1 from its rewards and the held table
-            const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
-            const int ca = (r + HA) * ly.aw + (c + HA);
+            int ca;
+            if constexpr (SLOT) {
+              ca = ca_of(rc[u]);
+            } else {
+              const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
+              ca = (r + HA) * ly.aw + (c + HA);
+            }
             mdp = prev_max_diff<M2>(sRew, ca, ly.aw);
             atdv = prev_diag_td<ALG>(q[u], qb[u], e, (b >> 4) & 1, sRew[ca], hp, eps_prev, &qe);
           } else {
@@ -1469,7 +1518,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   }
   if (!acting) {  // flush launch or absorbing iteration: persist the finalized Q
 #pragma unroll
-    for (int u = 0; u < APT; ++u) store_q<QB>(Qr, (uint32_t)n, agent_of(rc[u]), q[u], qb[u]);
+    for (int u = 0; u < APT; ++u) store_q<QB>(Qr, (uint32_t)n, AGENT_U(u), q[u], qb[u]);
     stored = true;
   }
   // the ring cells' border records (landed during phase 1a) to LDS for phase 1c:
@@ -1508,22 +1557,32 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
 #pragma unroll
     for (int u = 0; u < APT; ++u) {
       if (fin_only) continue;
-      const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
+      const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;   // ((row, column) word: not SLOT)
       const uint32_t one = owned(u);
       const double vmu = one ? 1.0 : 0.0;
-      const int cs = (r + HS) * ly.sw + (c + HS);
-      const int ca = (r + HA) * ly.aw + (c + HA);
+      const int ca = SLOT ? ca_of(rc[u]) : (r + HA) * ly.aw + (c + HA);
       const int s_t = (rc[u] >> 3) & 1;                     // (S_t bits, recorded in phase 1a)
-      const double P = payoff_pc(sPC, r + HA, c + HA, tab + (s_t ? 6 : 0), hp.norm_min, hp.norm_den,
-                                 hp.norm_rcp);
-      const RVal<RQ> r_t = AS ? hload<PERSIST>(at(Rin, agent_of(rc[u]))) : sRv[ca];
+      // (SLOT: the plus-count cell is the region cell, the pitches agree)
+      const double P = SLOT ? payoff_pc<PCP>(sPC, 0, ca, tab + (s_t ? 6 : 0), hp.norm_min, hp.norm_den, hp.norm_rcp)
+                            : payoff_pc<PCP>(sPC, r + HA, c + HA, tab + (s_t ? 6 : 0), hp.norm_min, hp.norm_den,
+                                             hp.norm_rcp);
+      const RVal<RQ> r_t = AS ? hload<PERSIST>(at(Rin, AGENT_U(u))) : sRv[ca];
       if constexpr (RQ) rsum += one ? r_t : 0;             // spgg.py:394 (units)
       else rsum = __builtin_fma(r_t, vmu, rsum);
       if (!acting) continue;
       if constexpr (PAIRED) {
         if (u % 2 == 0) {  // even lane: block of slot u, odd lane: slot u+1; swap halves
           const bool odd = tid & 1;
-          const uint2 w = philox_block((int)agent_of(rc[odd ? u + 1 : u]), t, pkey);
+          uint32_t gb;  // the block's agent
+          if constexpr (SLOT) {
+            // (both read first: a select between two array entries is folded into one load at a
+            // computed index, which keeps the array in scratch memory)
+            const uint32_t ge = gi[u], go = gi[u + 1];
+            gb = odd ? go : ge;
+          } else {
+            gb = agent_of(rc[odd ? u + 1 : u]);
+          }
+          const uint2 w = philox_block((int)gb, t, pkey);
           const uint32_t keep = odd ? w.y : w.x, recv = partner<1>(odd ? w.x : w.y);
           pbits[u] = odd ? recv : keep;
           pbits[u + 1] = odd ? keep : recv;
@@ -1536,7 +1595,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       int ex, rbt;                                          // algorithms.py:105-109
       if constexpr (PAIRED) philox_decide(pbits[u], eps53, &ex, &rbt);
       else if constexpr (DSTAGE) staged_draw(sDP, r + HA, c + HA, &ex, &rbt);
-      else draw_pair<RNG>(a, rep, agent_of(rc[u]), t, pkey, eps53, 0, &ex, &rbt);
+      else draw_pair<RNG>(a, rep, AGENT_U(u), t, pkey, eps53, 0, &ex, &rbt);
       double qs0, qs1;
       select_row<QB>(q[u], qb[u], so, &qs0, &qs1);
       const int act = ex ? rbt : greedy2(qs0, qs1);         // argmax ties -> 0
@@ -1594,7 +1653,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
           }
         }
       }
-      const double P = payoff_pc(sPC, ay, ax, tab + ((b & 1) ? 6 : 0), hp.norm_min, hp.norm_den, hp.norm_rcp);
+      const double P = payoff_pc<PCP>(sPC, ay, ax, tab + ((b & 1) ? 6 : 0), hp.norm_min, hp.norm_den, hp.norm_rcp);
       const RVal<RQ> r_t = AS ? RVal<RQ>(0) : RVal<RQ>(sRv[ay * ly.aw + ax]);
       int ex, rbt;
       if constexpr (DSTAGE) staged_draw(sDP, ay, ax, &ex, &rbt);
@@ -1629,8 +1688,8 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     const bool diag_on = ni_on && !RECOMP;
 #pragma unroll
     for (int u = 0; u < APT; ++u) {
-      const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
-      const int ca = (r + HA) * ly.aw + (c + HA);
+      const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;   // ((row, column) word: not SLOT)
+      const int ca = SLOT ? ca_of(rc[u]) : (r + HA) * ly.aw + (c + HA);
       const uint32_t one = owned(u);
       const int act = rc[u] & 1, so = (rc[u] >> 1) & 1;
       const double rew = sRew[ca];
@@ -1638,14 +1697,14 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       if constexpr (AS) sn = act == 0 ? 1 : 0;
       else sn = rep_state_lds<M2>(sRn, ca, ly.aw);
       double rn0, rn1;  // row s_{t+1} of the updated table (the border record's)
-      const float atd = td_update<ALG, RNG>(a, hp, rep, agent_of(rc[u]), t, pkey, eps_t, eps53, diag_on, rew, so,
+      const float atd = td_update<ALG, RNG>(a, hp, rep, AGENT_U(u), t, pkey, eps_t, eps53, diag_on, rew, so,
                                             act, sn, q[u], qb[u], &rn0, &rn1);
       if constexpr (CARRY) atd_own[u] = atd;  // (carried to the next iteration's phase 1a)
-      else if (diag_on) *at(atdr, agent_of(rc[u])) = atd;  // read only for the NI percent (0 when kappa == 0)
+      else if (diag_on) *at(atdr, AGENT_U(u)) = atd;  // read only for the NI percent (0 when kappa == 0)
       // the rows this launch changed: the TD row (so) and the NI row of t-1 (phase 1a)
       if (!PERSIST) {
         const uint32_t rows = ((ni_rows >> (2 * u)) & 3u) | (1u << so);
-        store_q<QB>(Qr, (uint32_t)n, agent_of(rc[u]), q[u], qb[u], rows);
+        store_q<QB>(Qr, (uint32_t)n, AGENT_U(u), q[u], qb[u], rows);
       }
       // neighbour influence, spgg.py:477-494: first argmax wins ties
       const int w = ly.aw;
@@ -1679,9 +1738,9 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       // max(0, max_diff) feeds only the next launch's NI term, which is +0 when kappa == 0
       // (phase 1a and the ring skip it): not stored then (-8 B/agent-step for those replicas)
       if constexpr (CARRY) md_own[u] = mdp;
-      else if (ni_on && !RECOMP) *at(mdr, agent_of(rc[u])) = mdp;
-      hstore<PERSIST>(at(Sout, agent_of(rc[u])), (uint8_t)((rc[u] & 0xff) | (dp << 2) | (sn << 4)));
-      hstore<PERSIST>(at(Rout, agent_of(rc[u])), (RT)sRn[ca]);
+      else if (ni_on && !RECOMP) *at(mdr, AGENT_U(u)) = mdp;
+      hstore<PERSIST>(at(Sout, AGENT_U(u)), (uint8_t)((rc[u] & 0xff) | (dp << 2) | (sn << 4)));
+      hstore<PERSIST>(at(Rout, AGENT_U(u)), (RT)sRn[ca]);
       const int bslot = (int)(int16_t)(uint16_t)(bsw >> (16 * u));  // (table: border_slot_table)
       if (bslot >= 0) {  // row s_{t+1} + max_diff for the neighbours' ring
         double* rec = pout + bslot;
@@ -1807,15 +1866,17 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       const bool ni_rec = __builtin_amdgcn_readfirstlane((int)(a0.params[rep].kappa != 0.0)) != 0;
 #pragma unroll
       for (int u = 0; u < APT; ++u) {
-        store_q<QB>(Qr, (uint32_t)n, agent_of(rc[u]), q[u], qb[u]);
+        store_q<QB>(Qr, (uint32_t)n, AGENT_U(u), q[u], qb[u]);
         if (CARRY && !RECOMP && ni_rec) {
-          *at(mdr, agent_of(rc[u])) = md_own[u];
-          *at(atdr, agent_of(rc[u])) = atd_own[u];
+          *at(mdr, AGENT_U(u)) = md_own[u];
+          *at(atdr, AGENT_U(u)) = atd_own[u];
         }
       }
     }
   }
 }
+
+#undef AGENT_U
 
 template <bool M2, bool AS, bool RQ, int RNG, int APT, int TWC, int ALG>
 __global__ __launch_bounds__(kBlock, min_waves(M2, RNG, TWC, ALG)) void spgg_step_kernel(TileArgs a, int t,
@@ -2795,7 +2856,7 @@ int spgg_create(spgg_ctx** out, const spgg_config* cfg) {
   if (!rc) rc = build_ring_table(c);
   if (!rc) {  // + the ring cells' border records (or the S_{t-1} plus-count plane that shares them)
     c->lds_bytes += std::max((size_t)c->ring_max * spgg_impl::pf_of(cfg->algorithm) * sizeof(double),
-                             (size_t)(ly.ah + 2) * kPcPitch);
+                             (size_t)(ly.ah + 2) * ly.pcp);
     if (c->lds_bytes > 160 * 1024) rc = fail(c, SPGG_E_ARG, "tile LDS footprint exceeds 160 KB");
   }
   // persistent launches (opt-in, SPGG_PERSIST=1): when the whole batch's tiles (every replica
