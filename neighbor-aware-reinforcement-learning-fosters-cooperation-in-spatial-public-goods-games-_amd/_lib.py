@@ -40,6 +40,9 @@ DW_NEVER, DW_NEVER_C, DW_SAME, DW_BOTH_C, DW_NCOOP, DW_FLIPS, DW_COOP_TIME, DW_A
 DWELL_AGE_BINS = 27
 DWELL_SLOTS = DW_AGE0 + 2 * DWELL_AGE_BINS   # 61
 
+# policy record row layout (spgg_abi.h): 16 counts, 4 + 1 bonds, then the 2 x 2 gap histograms of bins + 2 slots
+POLICY_COUNTS = 21   # SPGG_POLICY_COUNTS
+
 EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create", "spgg_set_params",
             "spgg_bind", "spgg_step", "spgg_step_groups", "spgg_flush", "spgg_draw", "spgg_payoff", "spgg_tile_shape",
             "spgg_destroy", "spgg_draw_planes", "spgg_pub_doubles", "spgg_stat_stripes",
@@ -48,7 +51,8 @@ EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create
             "spgg_status", "spgg_persistent", "spgg_clusters", "spgg_clusters_max_side",
             "spgg_correlations", "spgg_correlations_max_side", "spgg_reputation_hist",
             "spgg_reputation_pairs", "spgg_reputation_max_side", "spgg_dwell_bind", "spgg_dwell_reset",
-            "spgg_dwell_record", "spgg_dwell_fields", "spgg_clusters_tiled", "spgg_clusters_tiled_workspace")
+            "spgg_dwell_record", "spgg_dwell_fields", "spgg_clusters_tiled", "spgg_clusters_tiled_workspace",
+            "spgg_policy")
 # test-only entry points (include/spgg_test.h): exported by the library, not part of the product ABI
 TEST_EXPORTED = ("spgg_test_set_error",)
 
@@ -154,6 +158,8 @@ def load(path: str | None = None):
         lib.spgg_dwell_record.argtypes = [vp, i32, vp, ctypes.c_int64, vp]
         lib.spgg_dwell_fields.restype = ctypes.c_int
         lib.spgg_dwell_fields.argtypes = [vp, i32, vp, ctypes.c_int64, vp]
+        lib.spgg_policy.restype = ctypes.c_int
+        lib.spgg_policy.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.c_int64, vp]
         lib.spgg_persistent.restype = ctypes.c_int
         lib.spgg_persistent.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         lib.spgg_destroy.restype = ctypes.c_int

@@ -27,7 +27,8 @@ UNITS += [(os.path.join(CSRC, f"spgg_{name}.hip"), (), f"{name}.o")
                        "correlations",     # pair counts
                        "reputation",       # reputation record
                        "dwell",            # strategy dwell record
-                       "clusters_tiled")]  # cluster labelling over many workgroups
+                       "clusters_tiled",   # cluster labelling over many workgroups
+                       "policy")]          # learned policy record
 SRC = list(dict.fromkeys(u[0] for u in UNITS))  # the distinct source files
 INC = os.path.join(ROOT, "include")
 OUT = os.path.join(PKG_DIR, "libspgg_hip.so")

@@ -52,6 +52,7 @@
 #include "spgg_correlations.h"
 #include "spgg_reputation.h"
 #include "spgg_dwell.h"
+#include "spgg_policy.h"
 
 using namespace spgg;
 using namespace spgg_gen;
@@ -2230,6 +2231,10 @@ struct spgg_ctx {
   uint8_t* dwell_ref = nullptr;
   bool dwell_armed = false;
   int dwell_t_ref = 0;
+  // what spgg_policy needs to know of the table in place: the last iteration enqueued in this run
+  // (0: none) and whether spgg_flush has finalized it since (set in the step and flush paths)
+  int last_step = 0;
+  bool flushed = false;
   std::string err;
 };
 
@@ -2996,6 +3001,8 @@ static int step_setup(spgg_ctx* c) {
 
 static int step_begin(spgg_ctx* c, int32_t t0, int32_t n_steps, hipStream_t s) {
   if (t0 == 1) c->params_moved = false;  // a new run
+  if (t0 == 1) c->last_step = 0, c->flushed = false;
+  if (n_steps > 0) c->last_step = t0 + n_steps - 1, c->flushed = false;
   if (t0 == 1 && c->dwell_t_ref != 1) c->dwell_armed = false;  // a dwell reference of an earlier run is dropped
   const bool mt = c->cfg.rng_mode == SPGG_RNG_MT19937;
   int rc = step_setup(c);
@@ -3131,6 +3138,8 @@ int spgg_flush(spgg_ctx* c, int32_t t_last, void* stream) {
     spgg_gen::launch_final(gen_args(c), t_last, c->cfg.n_rep, s);
   }
   launch_step(c, t_last + 1, 1, s);
+  c->last_step = t_last;
+  c->flushed = true;
   return hip_check(c, hipGetLastError(), "spgg_flush launch");
 }
 
@@ -3287,6 +3296,29 @@ int spgg_dwell_fields(spgg_ctx* c, int32_t t, int32_t* out, int64_t out_stride, 
   spgg_dw::launch_fields(lattices(c), t, c->dwell_t_ref, c->dwell_words, out, out_stride,
                          reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_dwell_fields launch");
+}
+
+int spgg_policy(spgg_ctx* c, int32_t t, int32_t bins, const double* edges, uint8_t* plane, int32_t* out,
+                int64_t out_stride, void* stream) {
+  if (const int rc = observable_check(c, "spgg_policy", edges && plane && out, true, t)) return rc;
+  if (bins < 1 || bins > spgg_po::kMaxBins)
+    return fail(c, SPGG_E_ARG, "spgg_policy: bins = " + std::to_string(bins) + " outside 1 .. " +
+                                   std::to_string(spgg_po::kMaxBins));
+  if (out_stride < spgg_po::width(bins))
+    return fail(c, SPGG_E_ARG, "spgg_policy: out_stride below " + std::to_string(spgg_po::width(bins)));
+  if (c->persist)
+    return fail(c, SPGG_E_STATE, "spgg_policy: the context steps in persistent launches (spgg_persistent)");
+  if (c->params_moved)  // the NI term would be rebuilt from other parameters than the run's
+    return fail(c, SPGG_E_STATE, "spgg_policy: replica parameters changed mid-run (spgg_set_params)");
+  // Q exists only in place: the table of any other iteration is gone (or not there yet)
+  if (t != c->last_step + 1)
+    return fail(c, SPGG_E_STATE, "spgg_policy: t = " + std::to_string(t) + ", but the table in place is that of "
+                                 "iteration " + std::to_string(c->last_step + 1) + " (the one after the last enqueued)");
+  const spgg_po::Tables tb{c->buf.Q, c->buf.stats, c->d_params, c->stripes, c->cfg.iterations + 2,
+                           c->cfg.algorithm == SPGG_ALG_DOUBLE_Q, c->cfg.second_order != 0,
+                           c->cfg.state_mode == SPGG_STATE_ACTION, !c->flushed};
+  spgg_po::launch(lattices(c), tb, t, bins, edges, plane, out, out_stride, reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_policy launch");
 }
 
 int spgg_status(const spgg_ctx* c, uint32_t* flags) {

@@ -33,6 +33,7 @@ import torch
 from . import _lib as C
 from .algorithms import canonical_name
 from .dwell import DWELL_SLOTS, Dwell
+from .policy import Policy, policy_bin_edges, policy_width, split_row
 from .records import (KINDS, next_boundary, clusters_cap_text,  # noqa: F401  (the host models stay importable from here)
                       host_cluster_sizes, host_pair_counts, correlation_function, correlation_length,
                       reputation_bin_edges, host_reputation_pair_sums, reputation_correlation_function)
@@ -333,6 +334,7 @@ class BatchEngine:
         self._final_cache = {}     # final-state observables (cluster_sizes, pair_counts, ...) until the next step
         self.dwell_t_ref = None    # the reference iteration of the strategy dwell record while it is tracked
         self._clusters_work = None   # the workspace of spgg_clusters_tiled, allocated on first use
+        self._policy_work = None     # the (R, n) uint8 plane of spgg_policy, allocated on first use
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -678,6 +680,7 @@ class BatchEngine:
             for g in self.groups:
                 if g["live"] and np.all(self.stopped[g["r0"]:g["r1"]] != 0):
                     g["live"] = False
+                    g["t_retired"] = self.t   # the iteration after the last one enqueued on its context
         return bool(np.all(self.stopped != 0))
 
     def _loop_stream(self):
@@ -702,7 +705,7 @@ class BatchEngine:
             clusters_periodic: bool = False, correlations_every: int = 0,
             correlations_max_d: Optional[int] = None, reputation_every: int = 0,
             reputation_bins: int = 20, reputation_max_d: Optional[int] = None, dwell_every: int = 0,
-            clusters_tiled=False):
+            clusters_tiled=False, policy_every: int = 0, policy_bins: int = 32, policy_gap_range=2.0):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -736,7 +739,15 @@ class BatchEngine:
         (spgg_dwell_record: persistence, autocorrelation, flips, cooperator time, strategy ages) on the
         same schedule; read with dwell_histories().  A run continued with the same k keeps its record
         and its reference, another k starts afresh at the current t, 0 stops the tracking of an
-        earlier run and drops its record; not on an engine that steps in persistent launches."""
+        earlier run and drops its record; not on an engine that steps in persistent launches.
+        policy_every = k > 0 records the learned policy field (spgg_policy, policy.py: the sixteen counts
+        class x strategy x state of the tables the agents act on at t -- the pending neighbour-influence
+        term rebuilt on the device --, the bonds between like and unlike classes and the histograms of
+        the two action gaps over policy_bins bins across policy_gap_range, a number g for (-g, g) or a
+        (lo, hi) pair, with a slot below and one above) on the same schedule; read with
+        policy_histories().  Settings as for the other records; not on an engine that steps in
+        persistent launches."""
+        policy_key = Policy.validate(self, policy_every, policy_bins, policy_gap_range)   # (before any allocation)
         asked = {"clusters": (clusters_every, clusters_periodic, clusters_tiled), "correlations": (correlations_every, correlations_max_d),
                  "reputation": (reputation_every, reputation_bins, reputation_max_d)}
         keys = {name: KINDS[name].validate(self, *a) for name, a in asked.items()}   # (before any allocation)
@@ -757,6 +768,13 @@ class BatchEngine:
             active.append(rec)
         elif "dwell" in self.records:
             self.dwell_stop()
+        if policy_key[0]:
+            rec = self.records.get("policy")
+            if rec is None or rec.key != policy_key:
+                rec = self.records["policy"] = Policy(policy_key[0], self.t, self.T, policy_key)
+                rec.plan = rec.calls(self)
+                rec.out = [torch.zeros((self.R, rec.rows, policy_width(policy_key[1])), dtype=torch.int32, device=self.dev)]
+            active.append(rec)
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -1081,6 +1099,61 @@ class BatchEngine:
         flip_total_history, cooperator_time_history (m,) and strategy_age_hist_history
         (m, 2, DWELL_AGE_BINS), all int64."""
         return self._histories("dwell", "dwell_histories: run(dwell_every=k)")
+
+    # -- the learned policy record (policy.py; spgg_policy) --------------------
+    def _spgg_policy(self, ctx, t, *rest):
+        """spgg_policy on one group's context.  The call names the iteration after the last one enqueued
+        on that context: a group retired mid-run (every replica absorbed) is stepped no further, so its
+        context stays at the iteration it was retired at until the flush -- its replicas' records are
+        those of their absorbing iterations whichever t is given."""
+        g = next(g for g in self.groups if g["ctx"] is ctx)
+        if not g["live"] and not self._flushed:
+            t = g["t_retired"]
+        return self.lib.spgg_policy(ctx, int(t), *rest)
+
+    def _policy_plane(self):
+        """The (R, n) uint8 plane spgg_policy writes (class | strategy << 2 | state << 3), allocated once."""
+        if self._policy_work is None:
+            self._policy_work = torch.empty((self.R, self.n), dtype=torch.uint8, device=self.dev)
+        return self._policy_work
+
+    def _policy_edges(self, bins, gap_range):
+        """Device f64 (R, bins + 1): the gap histogram's edges, the same for every replica."""
+        e = np.tile(policy_bin_edges(gap_range, bins), (self.R, 1))
+        return torch.from_numpy(e).to(self.dev)
+
+    def _policy_final(self, bins, gap_range, what):
+        key = Policy.validate(self, 1, bins, gap_range, what)
+        ck = ("policy",) + key[1:]
+        if ck not in self._final_cache:
+            self._final(ck, self._spgg_policy, (key[1], self._policy_edges(key[1], key[2]), self._policy_plane()),
+                        policy_width(key[1]))
+            self._final_cache["policy_plane"] = self._policy_plane().cpu().numpy().reshape(self.R, self.L, self.L)
+        return self._final_cache[ck]
+
+    def policy_record(self, k, bins: int = 32, gap_range=2.0) -> dict:
+        """The policy record of replica k in the state the engine is in (after run(): the state
+        final_state(k) returns; between two step() calls: the tables the agents act on next, the
+        pending neighbour-influence term included): counts int64 (4, 2, 2) class x strategy x state,
+        bonds (5,) bonds_same[0 .. 3] and bonds_mixed, gap_hist (2, 2, bins + 2) strategy x state x
+        slot, and gap_bin_edges (policy.py).  Counted on the device, all replicas at once, and cached
+        until the engine steps again."""
+        counts, bonds, hist = split_row(self._policy_final(bins, gap_range, "policy_record")[k], int(bins))
+        return dict(counts=counts.copy(), bonds=bonds.copy(), gap_hist=hist.copy(),
+                    gap_bin_edges=policy_bin_edges(gap_range, int(bins)))
+
+    def policy_map(self, k) -> np.ndarray:
+        """(L, L) uint8 map of replica k in that state: class | strategy << 2 | state << 3 per agent."""
+        if "policy_plane" not in self._final_cache:    # (any policy_record call of this state left it)
+            self._policy_final(32, 2.0, "policy_map")
+        return self._final_cache["policy_plane"][k].copy()
+
+    def policy_histories(self):
+        """Per replica, the in-run policy record of run(policy_every=k) (policy.POLICY_DATASETS):
+        policy_history_iters (the recorded iterations t <= last_iteration), policy_count_history int64
+        (m, 4, 2, 2), policy_bond_history (m, 5), policy_gap_hist_history (m, 2, 2, bins + 2) and
+        policy_gap_bin_edges f64 (bins + 1,)."""
+        return self._histories("policy", "policy_histories: run(policy_every=k)")
 
     def finalize_history(self):
         """Derived history slots (payoff sums, w_P*P, w_rep*rr, reward over D) of every

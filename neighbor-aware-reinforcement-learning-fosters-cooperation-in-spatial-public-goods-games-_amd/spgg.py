@@ -18,6 +18,7 @@ from . import algorithms as A
 from .dwell import DWELL_DATASETS, DWELL_FIELD_DATASETS
 from .engine import BatchEngine, InitState, ReplicaParams, SNAPSHOT_ITERS
 from .h5io import open_writer
+from .policy import POLICY_DATASETS, POLICY_MAP_DATASET
 
 
 def _sum5(A_):
@@ -66,6 +67,20 @@ DWELL_OPTIONS = {
 }
 
 
+# The learned policy record's options (policy.py), class attributes of SPGG in a table of their own as
+# the dwell record's are.  name -> (default, conversion).  policy_history_every = k > 0: record the
+# policy field (classes by strategy and state, bonds, gap histograms) at t = 1, 1+k, ... on the device
+# and write the POLICY_DATASETS after the dwell datasets; _bins and _gap_range (a number g for (-g, g),
+# or a (lo, hi) pair): the gap histogram; policy_map_final: also the final state's per-agent map
+# class | strategy << 2 | state << 3 (uint8) as POLICY_MAP_DATASET.
+POLICY_OPTIONS = {
+    "policy_history_every": (0, _count),
+    "policy_history_bins": (32, int),
+    "policy_history_gap_range": (2.0, lambda v: v),
+    "policy_map_final": (False, bool),
+}
+
+
 def _tiled(v):
     return v if isinstance(v, bool) else (int(v) if v else False)
 
@@ -107,6 +122,27 @@ def dwell_histories(eng, every, fields):
     return hist
 
 
+def policy_option_values(values):
+    """(BatchEngine.run's policy keyword arguments, policy_map_final) from option values (a mapping;
+    absent: default)."""
+    every, bins, gap_range, final = (conv(values.get(name, default)) for name, (default, conv) in POLICY_OPTIONS.items())
+    if final and not every:
+        raise ValueError("policy_map_final needs policy_history_every > 0 (nothing is recorded otherwise)")
+    return dict(policy_every=every, policy_bins=bins, policy_gap_range=gap_range), final
+
+
+def policy_histories(eng, run_kw, map_final):
+    """write_datasets' policy_hist of every replica of a run(**run_kw): the engine's policy_histories,
+    with map_final also the final state's map; None without the record."""
+    if not run_kw["policy_every"]:
+        return None
+    hist = eng.policy_histories()
+    if map_final:
+        for k, h in enumerate(hist):
+            h[POLICY_MAP_DATASET] = eng.policy_map(k)
+    return hist
+
+
 def record_run_kwargs(values):
     """BatchEngine.run's record keyword arguments from option values (a mapping; absent: default)."""
     return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in RECORD_OPTIONS.items()}
@@ -116,7 +152,7 @@ class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
-    # (the RECORD_OPTIONS, DWELL_OPTIONS and CLUSTER_TILED_OPTIONS are class attributes too, set at their defaults
+    # (the RECORD_OPTIONS, DWELL_OPTIONS, CLUSTER_TILED_OPTIONS and POLICY_OPTIONS are class attributes too, set at their defaults
     # below the class)
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
@@ -227,11 +263,13 @@ class SPGG:
             records = record_run_kwargs({name: getattr(self, name) for name in RECORD_OPTIONS})
             dwell_every, dwell_fields = dwell_option_values({name: getattr(self, name) for name in DWELL_OPTIONS})
             tiled = cluster_tiled_run_kwargs({name: getattr(self, name) for name in CLUSTER_TILED_OPTIONS})
-            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records, **tiled)
+            policy_kw, policy_map = policy_option_values({name: getattr(self, name) for name in POLICY_OPTIONS})
+            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records, **tiled, **policy_kw)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (over many workgroups above side 200)
             record_hists = {arg: h and h[0] for arg, h in record_histories(eng, records).items()}
             dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
+            policy_hist = policy_histories(eng, policy_kw, policy_map)
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -262,7 +300,8 @@ class SPGG:
         # the datasets last: the reference fills its file after the loop, so a write
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
-                       clusters=clusters, dwell_hist=dwell_hist and dwell_hist[0], **record_hists)
+                       clusters=clusters, dwell_hist=dwell_hist and dwell_hist[0],
+                       policy_hist=policy_hist and policy_hist[0], **record_hists)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -274,6 +313,8 @@ for _name, (_default, _kw, _conv) in RECORD_OPTIONS.items():
 for _name, (_default, _conv) in DWELL_OPTIONS.items():
     setattr(SPGG, _name, _default)
 for _name, (_default, _kw, _conv) in CLUSTER_TILED_OPTIONS.items():
+    setattr(SPGG, _name, _default)
+for _name, (_default, _conv) in POLICY_OPTIONS.items():
     setattr(SPGG, _name, _default)
 
 
@@ -312,7 +353,7 @@ def record_histories(eng, run_kwargs):
 
 
 def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
-                   cluster_hist=None, correlation_hist=None, reputation_hist=None, dwell_hist=None):
+                   cluster_hist=None, correlation_hist=None, reputation_hist=None, dwell_hist=None, policy_hist=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
     the final state.  Shared by SPGG.run and the batched sweep runner.
@@ -324,7 +365,9 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
     reputation_hist: the in-run reputation record (BatchEngine.reputation_histories), written as
     the REPUTATION_DATASETS it holds after those; dwell_hist: the in-run strategy dwell record
     (BatchEngine.dwell_histories), written as the DWELL_DATASETS after those, then the
-    DWELL_FIELD_DATASETS it holds (int64; cooperation_frequency_final f64).
+    DWELL_FIELD_DATASETS it holds (int64; cooperation_frequency_final f64); policy_hist: the in-run
+    policy record (BatchEngine.policy_histories), written as the POLICY_DATASETS after those (int64;
+    policy_gap_bin_edges f64), then POLICY_MAP_DATASET (uint8) if it holds it.
     The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
@@ -366,6 +409,11 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
             if name in dwell_hist or name in DWELL_DATASETS:
                 data_file.create_dataset(name, data=np.asarray(
                     dwell_hist[name], dtype=np.float64 if name == "cooperation_frequency_final" else np.int64))
+        for name in POLICY_DATASETS if policy_hist is not None else ():
+            data_file.create_dataset(name, data=np.asarray(
+                policy_hist[name], dtype=np.float64 if name == "policy_gap_bin_edges" else np.int64))
+        if policy_hist is not None and POLICY_MAP_DATASET in policy_hist:
+            data_file.create_dataset(POLICY_MAP_DATASET, data=np.asarray(policy_hist[POLICY_MAP_DATASET], dtype=np.uint8))
 
 
 def track_positions(L):

@@ -1,6 +1,6 @@
-"""What the device records cost (profiles/{clusters,correlations,reputation,dwell}/README.txt).
+"""What the device records cost (profiles/{clusters,correlations,reputation,dwell,policy}/README.txt).
 
-    python tools/record_cost.py --record clusters|correlations|reputation|dwell [--repeats 5] [--iters 10000]
+    python tools/record_cost.py --record clusters|correlations|reputation|dwell|policy [--repeats 5] [--iters 10000]
                                 [--legs LEG,LEG,...]
 
 Every variant runs in a fresh process (this driver never touches the GPU) and reports the median of
@@ -32,6 +32,12 @@ its repeats.  Legs (default: all of the record's, in this order):
                        and with the dwell launch armed, in one process, after 20 and after 400
                        iterations: the difference is the dwell launch's own cost; variant CONFIG:T
                 record device time of one spgg_dwell_record round / one spgg_dwell_fields round
+  policy        call   device time of one spgg_policy round (three launches: zero, policy, bonds; 32 bins)
+                       at cfg3's, cfg4's and cfg5's shapes after 200 iterations, the table in place still
+                       without its pending term (the in-run case: the term is rebuilt) and flushed; the
+                       fraction of the byte floor at 8 TB/s; variant CONFIG:pending|flushed
+                run    the whole run (BatchEngine.run, MT19937) of cfg3, cfg4 and cfg5 with policy_every
+                       0 / 100 / 10 / 1; variant CONFIG:EVERY:ITERATIONS
   every other   run    the whole cfg3 run (BatchEngine.run, MT19937, as bench.full_run times it) with
                        the record every {0, 16, 1} iterations (max_d = 100, 20 bins)
 """
@@ -51,14 +57,15 @@ BINS = 20
 SHAPES = ["cfg3", "cfg4", "cfg5"]
 
 
-def _engine_at(config, t, T, rng="philox"):
+def _engine_at(config, t, T, rng="philox", flush=True):
     import torch
     import bench
     from spgg_amd.engine import BatchEngine
     _desc, L, M2, state, reps = bench.workload(config, 0)
     eng = BatchEngine(L, T, reps, use_second_order=M2, state_representation=state, rng=rng)
     eng.step(t)
-    eng.flush()
+    if flush:
+        eng.flush()
     torch.cuda.synchronize()
     eng.all_stopped()
     return eng
@@ -359,6 +366,56 @@ def leg_dwell_record(a):
         eng.close()
 
 
+POLICY_BINS = 32
+FLOOR_BYTES_PER_SECOND = 8e12   # cache-resident reads as this project has measured them (7.4-8.6 TB/s)
+
+
+def leg_policy_call(a):
+    import torch
+    from spgg_amd.policy import policy_width
+    config, table = a.variant.split(":")
+    eng = _engine_at(config, 200, 300, flush=table == "flushed")
+    try:
+        width = policy_width(POLICY_BINS)
+        out_buf = torch.zeros((eng.R, width), dtype=torch.int32, device=eng.dev)
+        edges, plane = eng._policy_edges(POLICY_BINS, (-2.0, 2.0)), eng._policy_plane()
+        us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_policy(
+            g["ctx"], eng.t, POLICY_BINS, edges[g["r0"]].data_ptr(), plane[g["r0"]].data_ptr(),
+            out_buf[g["r0"]].data_ptr(), width, s))
+        got = out_buf.cpu().numpy()
+        assert (got[:, :16].sum(axis=1) == eng.n).all() and (got[:, 16:21].sum(axis=1) == 2 * eng.n).all()
+        live = int((eng.stopped == 0).sum())
+        bytes_ = eng.R * eng.n * (eng.QW * 8 + 3)     # Q, the S byte, the plane byte written and read back
+        floor_us = bytes_ / FLOOR_BYTES_PER_SECOND * 1e6
+        return {"leg": "call", "variant": a.variant, "replicas": eng.R, "L": eng.L, "groups": eng.G, "live": live,
+                "MB": round(bytes_ / 1e6, 1), "floor_us": round(floor_us, 2),
+                "floor_fraction": [round(floor_us / u, 3) for u in us], "us_per_round": us}
+    finally:
+        eng.close()
+
+
+def leg_policy_run(a):
+    import torch
+    import bench
+    from spgg_amd.engine import BatchEngine
+    config, every, iters = a.variant.split(":")
+    _desc, L, M2, state, reps = bench.workload(config, 0)
+    out = []
+    for _ in range(a.repeats + 1):
+        eng = BatchEngine(L, int(iters), reps, use_second_order=M2, state_representation=state, rng="mt19937")
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.run(snapshots=False, policy_every=int(every), policy_bins=POLICY_BINS)
+            torch.cuda.synchronize()
+            out.append(time.perf_counter() - t0)
+            executed = eng.t - 1
+        finally:
+            eng.close()
+    return {"leg": "run", "variant": a.variant, "iterations": executed, "replicas": len(reps), "L": L,
+            "us_per_iter": [s / executed * 1e6 for s in out[1:]], "seconds": out[1:]}
+
+
 RUN = (leg_run, ["0", "16", "1"])
 LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
                      "call": (leg_call, [f"{c}:{s}:{p}" for c in ("cfg3", "cfg4") for s in ("record", "sizes")
@@ -372,7 +429,9 @@ LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
         "reputation": {"hist": (leg_call, SHAPES), "pairs": (leg_call, SHAPES), "host": (leg_host, SHAPES), "run": RUN},
         "dwell": {"run": (leg_dwell_run, [f"{c}:{e}:{i}" for c in SHAPES for i in ("iters", "400") for e in (0, 256, 16)]),
                   "launch": (leg_dwell_launch, [f"{c}:{t}" for c in SHAPES for t in (20, 400)]),
-                  "record": (leg_dwell_record, [f"{c}:{w}" for c in SHAPES for w in ("record", "fields")])}}
+                  "record": (leg_dwell_record, [f"{c}:{w}" for c in SHAPES for w in ("record", "fields")])},
+        "policy": {"call": (leg_policy_call, [f"{c}:{w}" for c in SHAPES for w in ("pending", "flushed")]),
+                   "run": (leg_policy_run, [f"{c}:{e}:iters" for c in SHAPES for e in (0, 100, 10, 1)])}}
 
 
 def main():
@@ -388,7 +447,7 @@ def main():
     if a.child:
         print("RESULT " + json.dumps(legs[a.child][0](a)), flush=True)
         return 0
-    width = 16 if a.record in ("clusters", "dwell") else 6
+    width = 16 if a.record in ("clusters", "dwell", "policy") else 6
     for leg in (a.legs.split(",") if a.legs else legs):
         for variant in legs[leg][1]:
             variant = variant.replace(":iters", f":{a.iters}")
