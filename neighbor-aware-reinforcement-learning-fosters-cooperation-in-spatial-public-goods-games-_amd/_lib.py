@@ -43,6 +43,10 @@ DWELL_SLOTS = DW_AGE0 + 2 * DWELL_AGE_BINS   # 61
 # policy record row layout (spgg_abi.h): 16 counts, 4 + 1 bonds, then the 2 x 2 gap histograms of bins + 2 slots
 POLICY_COUNTS = 21   # SPGG_POLICY_COUNTS
 
+# payoff census row layout (spgg_abi.h): census[sigma][m][K] (2 x 5 x 26), bond_cd[dK + 25] (51), bond_cc[|dK|] and
+# bond_dd[|dK|] (26 each)
+PAYOFF_SLOTS, PAYOFF_BOND_CD, PAYOFF_BOND_CC, PAYOFF_BOND_DD = 363, 260, 311, 337
+
 EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create", "spgg_set_params",
             "spgg_bind", "spgg_step", "spgg_step_groups", "spgg_flush", "spgg_draw", "spgg_payoff", "spgg_tile_shape",
             "spgg_destroy", "spgg_draw_planes", "spgg_pub_doubles", "spgg_stat_stripes",
@@ -52,7 +56,7 @@ EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create
             "spgg_correlations", "spgg_correlations_max_side", "spgg_reputation_hist",
             "spgg_reputation_pairs", "spgg_reputation_max_side", "spgg_dwell_bind", "spgg_dwell_reset",
             "spgg_dwell_record", "spgg_dwell_fields", "spgg_clusters_tiled", "spgg_clusters_tiled_workspace",
-            "spgg_policy")
+            "spgg_policy", "spgg_payoff_census", "spgg_payoff_pairs", "spgg_payoff_pairs_max_side")
 # test-only entry points (include/spgg_test.h): exported by the library, not part of the product ABI
 TEST_EXPORTED = ("spgg_test_set_error",)
 
@@ -160,6 +164,12 @@ def load(path: str | None = None):
         lib.spgg_dwell_fields.argtypes = [vp, i32, vp, ctypes.c_int64, vp]
         lib.spgg_policy.restype = ctypes.c_int
         lib.spgg_policy.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.c_int64, vp]
+        lib.spgg_payoff_census.restype = ctypes.c_int
+        lib.spgg_payoff_census.argtypes = [vp, i32, vp, vp, ctypes.c_int64, vp]
+        lib.spgg_payoff_pairs.restype = ctypes.c_int
+        lib.spgg_payoff_pairs.argtypes = [vp, i32, i32, vp, vp, ctypes.c_int64, vp]
+        lib.spgg_payoff_pairs_max_side.restype = ctypes.c_int
+        lib.spgg_payoff_pairs_max_side.argtypes = [vp, ctypes.POINTER(i32)]
         lib.spgg_persistent.restype = ctypes.c_int
         lib.spgg_persistent.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         lib.spgg_destroy.restype = ctypes.c_int

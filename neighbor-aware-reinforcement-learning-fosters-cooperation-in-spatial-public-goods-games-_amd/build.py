@@ -28,7 +28,8 @@ UNITS += [(os.path.join(CSRC, f"spgg_{name}.hip"), (), f"{name}.o")
                        "reputation",       # reputation record
                        "dwell",            # strategy dwell record
                        "clusters_tiled",   # cluster labelling over many workgroups
-                       "policy")]          # learned policy record
+                       "policy",           # learned policy record
+                       "payoff")]          # payoff record
 SRC = list(dict.fromkeys(u[0] for u in UNITS))  # the distinct source files
 INC = os.path.join(ROOT, "include")
 OUT = os.path.join(PKG_DIR, "libspgg_hip.so")

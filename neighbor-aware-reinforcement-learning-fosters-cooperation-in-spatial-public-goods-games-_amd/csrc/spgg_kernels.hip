@@ -52,6 +52,7 @@
 #include "spgg_correlations.h"
 #include "spgg_reputation.h"
 #include "spgg_dwell.h"
+#include "spgg_payoff.h"
 #include "spgg_policy.h"
 
 using namespace spgg;
@@ -3319,6 +3320,33 @@ int spgg_policy(spgg_ctx* c, int32_t t, int32_t bins, const double* edges, uint8
                            c->cfg.state_mode == SPGG_STATE_ACTION, !c->flushed};
   spgg_po::launch(lattices(c), tb, t, bins, edges, plane, out, out_stride, reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_policy launch");
+}
+
+int spgg_payoff_census(spgg_ctx* c, int32_t t, uint8_t* plane, int32_t* out, int64_t out_stride, void* stream) {
+  if (const int rc = observable_check(c, "spgg_payoff_census", out, false, t)) return rc;
+  if (out_stride < spgg_pf::kSlots)
+    return fail(c, SPGG_E_ARG, "spgg_payoff_census: out_stride below " + std::to_string(spgg_pf::kSlots));
+  spgg_pf::launch_census(lattices(c), t, plane, out, out_stride, reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_payoff_census launch");
+}
+
+int spgg_payoff_pairs_max_side(const spgg_ctx*, int32_t* side) {   // (a constant of the build: ctx may be null)
+  if (!side) return SPGG_E_ARG;
+  *side = spgg_pf::kMaxSide;
+  return SPGG_OK;
+}
+
+int spgg_payoff_pairs(spgg_ctx* c, int32_t t, int32_t max_d, const uint8_t* plane, int64_t* out, int64_t out_stride,
+                      void* stream) {
+  if (c && out && !plane)
+    return fail(c, SPGG_E_ARG, "spgg_payoff_pairs: no plane (the one a spgg_payoff_census call of the same t wrote)");
+  if (const int rc = observable_check(c, "spgg_payoff_pairs", out, false, t)) return rc;
+  if (const int rc = range_check(c, "spgg_payoff_pairs", spgg_pf::kMaxSide, "cell indices are int32", max_d)) return rc;
+  if (out_stride < spgg_pf::pairs_width(max_d))
+    return fail(c, SPGG_E_ARG, "spgg_payoff_pairs: out_stride below 2 + 6 * (max_d + 1)");
+  spgg_pf::launch_pairs(lattices(c), max_d, plane, reinterpret_cast<long long*>(out), out_stride,
+                        reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_payoff_pairs launch");
 }
 
 int spgg_status(const spgg_ctx* c, uint32_t* flags) {

@@ -33,6 +33,7 @@ import torch
 from . import _lib as C
 from .algorithms import canonical_name
 from .dwell import DWELL_SLOTS, Dwell
+from .payoff import PAYOFF_SLOTS, Payoff, pairs_width
 from .policy import Policy, policy_bin_edges, policy_width, split_row
 from .records import (KINDS, next_boundary, clusters_cap_text,  # noqa: F401  (the host models stay importable from here)
                       host_cluster_sizes, host_pair_counts, correlation_function, correlation_length,
@@ -335,6 +336,7 @@ class BatchEngine:
         self.dwell_t_ref = None    # the reference iteration of the strategy dwell record while it is tracked
         self._clusters_work = None   # the workspace of spgg_clusters_tiled, allocated on first use
         self._policy_work = None     # the (R, n) uint8 plane of spgg_policy, allocated on first use
+        self._payoff_work = None     # the (R, n) uint8 plane of spgg_payoff_census, allocated on first use
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -486,6 +488,8 @@ class BatchEngine:
             fn = getattr(self.lib, f"spgg_{kind}_max_side")
             C.check(fn(self.ctx, ctypes.byref(side)), self.ctx, fn.__name__)
             setattr(self, f"{kind}_max_side", int(side.value))
+        C.check(self.lib.spgg_payoff_pairs_max_side(self.ctx, ctypes.byref(side)), self.ctx, "spgg_payoff_pairs_max_side")
+        self.payoff_pairs_max_side = int(side.value)
 
     def _draw_layout(self, ctx):
         """(ring slots, u32 words per replica and slot, key-snapshot slots) of the draw records."""
@@ -705,7 +709,8 @@ class BatchEngine:
             clusters_periodic: bool = False, correlations_every: int = 0,
             correlations_max_d: Optional[int] = None, reputation_every: int = 0,
             reputation_bins: int = 20, reputation_max_d: Optional[int] = None, dwell_every: int = 0,
-            clusters_tiled=False, policy_every: int = 0, policy_bins: int = 32, policy_gap_range=2.0):
+            clusters_tiled=False, policy_every: int = 0, policy_bins: int = 32, policy_gap_range=2.0,
+            payoff_every: int = 0, payoff_max_d: Optional[int] = None):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -746,8 +751,16 @@ class BatchEngine:
         the two action gaps over policy_bins bins across policy_gap_range, a number g for (-g, g) or a
         (lo, hi) pair, with a slot below and one above) on the same schedule; read with
         policy_histories().  Settings as for the other records; not on an engine that steps in
+        persistent launches.
+        payoff_every = k > 0 records the payoff field (spgg_payoff_census, payoff.py: the census of the
+        agents by strategy, cooperating neighbours and group-cooperator total K -- the payoff
+        distribution for any parameters -- and the bonds between right / lower neighbours by their
+        difference in K; with payoff_max_d also spgg_payoff_pairs, the pair sums of K and c at the
+        distances 0 .. payoff_max_d) on the same schedule; read with payoff_histories().  Settings as
+        for the other records; a function of S_t alone, so allowed on an engine that steps in
         persistent launches."""
         policy_key = Policy.validate(self, policy_every, policy_bins, policy_gap_range)   # (before any allocation)
+        payoff_key = Payoff.validate(self, payoff_every, payoff_max_d)
         asked = {"clusters": (clusters_every, clusters_periodic, clusters_tiled), "correlations": (correlations_every, correlations_max_d),
                  "reputation": (reputation_every, reputation_bins, reputation_max_d)}
         keys = {name: KINDS[name].validate(self, *a) for name, a in asked.items()}   # (before any allocation)
@@ -775,6 +788,8 @@ class BatchEngine:
                 rec.plan = rec.calls(self)
                 rec.out = [torch.zeros((self.R, rec.rows, policy_width(policy_key[1])), dtype=torch.int32, device=self.dev)]
             active.append(rec)
+        if payoff_key[0]:
+            active.append(self._record("payoff", payoff_key, Payoff))
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -894,12 +909,12 @@ class BatchEngine:
                     g["ctx"], fn.__name__)
         self._enqueue(one)
 
-    def _record(self, name, key):
-        """The in-run Record `name` (records.KINDS) with the validated settings `key`: the one a run
-        with the same settings left, or a new one that starts at the current iteration."""
+    def _record(self, name, key, kind=None):
+        """The in-run Record `name` (of records.KINDS, or of the given class) with the validated settings
+        `key`: the one a run with the same settings left, or a new one that starts at the current iteration."""
         rec = self.records.get(name)
         if rec is None or rec.key != key:
-            rec = self.records[name] = KINDS[name](key[0], self.t, self.T, key)
+            rec = self.records[name] = (kind or KINDS[name])(key[0], self.t, self.T, key)
             rec.plan = rec.calls(self)
             rec.out = [torch.zeros((self.R, rec.rows, w), dtype=getattr(torch, dt), device=self.dev)
                        for _fn, _args, w, dt in rec.plan]
@@ -1154,6 +1169,50 @@ class BatchEngine:
         (m, 4, 2, 2), policy_bond_history (m, 5), policy_gap_hist_history (m, 2, 2, bins + 2) and
         policy_gap_bin_edges f64 (bins + 1,)."""
         return self._histories("policy", "policy_histories: run(policy_every=k)")
+
+    # -- the payoff record (payoff.py; spgg_payoff_census, spgg_payoff_pairs) --------------------
+    def _payoff_plane(self):
+        """The (R, n) uint8 plane spgg_payoff_census writes (K | strategy << 5 | m << 6), allocated once."""
+        if self._payoff_work is None:
+            self._payoff_work = torch.empty((self.R, self.n), dtype=torch.uint8, device=self.dev)
+        return self._payoff_work
+
+    def _payoff_final(self):
+        if "payoff_census" not in self._final_cache:
+            self._final("payoff_census", self.lib.spgg_payoff_census, (self._payoff_plane(),), PAYOFF_SLOTS)
+            self._final_cache["payoff_plane"] = self._payoff_plane().cpu().numpy().reshape(self.R, self.L, self.L)
+        return self._final_cache["payoff_census"]
+
+    def payoff_census(self, k) -> np.ndarray:
+        """int64 (PAYOFF_SLOTS,) census row of replica k in the state the engine is in (after run():
+        the state final_state(k) returns): census[sigma][m][K], bond_cd, bond_cc, bond_dd
+        (payoff.split_census).  Counted on the device, all replicas at once, and cached until the
+        engine steps again."""
+        return self._payoff_final()[k].copy()
+
+    def payoff_pair_sums(self, k, max_d: Optional[int] = None) -> np.ndarray:
+        """int64 (2 + 6 (D + 1),) pair-sum row of replica k in that state, D = max_d (None: L // 2): sum K,
+        sum c, then (KK, CK, CC) for d = 0 .. D along rows, then along columns (payoff.split_pairs), from
+        the plane the census of the same state wrote; cached like it."""
+        key = Payoff.validate(self, 1, self.L // 2 if max_d is None else max_d, "payoff_pair_sums")
+        self._payoff_final()      # (the plane of this state)
+        return self._final(("payoff_pairs", key[1]), self.lib.spgg_payoff_pairs, (key[1], self._payoff_plane()),
+                           pairs_width(key[1]), torch.int64)[k].copy()
+
+    def payoff_map(self, k) -> np.ndarray:
+        """(L, L) uint8 map of replica k in that state: K in bits 0-4, the strategy in bit 5;
+        payoff.payoff_values(params)[map >> 5 & 1, map & 31] is the payoff field.  Bits 6-7 hold only the low
+        two bits of m, the cooperating neighbours: 4 reads as 0 there.  Where m is wanted, take it from the
+        strategies (payoff.payoff_fields(map >> 5 & 1)[1]) or from the census, which holds it in full."""
+        self._payoff_final()
+        return self._final_cache["payoff_plane"][k].copy()
+
+    def payoff_histories(self):
+        """Per replica, the in-run payoff record of run(payoff_every=k) (payoff.PAYOFF_DATASETS):
+        payoff_history_iters (the recorded iterations t <= last_iteration), payoff_census_history int64
+        (m, 2, 5, 26), payoff_bond_history (m, 103: bond_cd, bond_cc, bond_dd) and payoff_values f64
+        (2, 26); with payoff_max_d also payoff_pair_sums_history (m, 2 + 6 (D + 1))."""
+        return self._histories("payoff", "payoff_histories: run(payoff_every=k)")
 
     def finalize_history(self):
         """Derived history slots (payoff sums, w_P*P, w_rep*rr, reward over D) of every

@@ -18,6 +18,7 @@ from . import algorithms as A
 from .dwell import DWELL_DATASETS, DWELL_FIELD_DATASETS
 from .engine import BatchEngine, InitState, ReplicaParams, SNAPSHOT_ITERS
 from .h5io import open_writer
+from .payoff import PAYOFF_DATASETS, PAYOFF_MAP_DATASET, PAYOFF_PAIRS_DATASET
 from .policy import POLICY_DATASETS, POLICY_MAP_DATASET
 
 
@@ -78,6 +79,20 @@ POLICY_OPTIONS = {
     "policy_history_bins": (32, int),
     "policy_history_gap_range": (2.0, lambda v: v),
     "policy_map_final": (False, bool),
+}
+
+
+# The payoff record's options (payoff.py), class attributes of SPGG in a table of their own as the policy
+# record's are.  name -> (default, conversion).  payoff_history_every = k > 0: record the payoff field
+# (the census of strategy x cooperating neighbours x group-cooperator total, and the bonds by their
+# difference in that total) at t = 1, 1+k, ... on the device and write the PAYOFF_DATASETS after the
+# policy datasets; payoff_max_distance not None: also the pair sums of K and c at the distances
+# 0 .. payoff_max_distance (PAYOFF_PAIRS_DATASET); payoff_map_final: also the final state's per-agent
+# map K | strategy << 5 | (m & 3) << 6 (uint8) as PAYOFF_MAP_DATASET.
+PAYOFF_OPTIONS = {
+    "payoff_history_every": (0, _count),
+    "payoff_max_distance": (None, lambda v: v),
+    "payoff_map_final": (False, bool),
 }
 
 
@@ -143,6 +158,28 @@ def policy_histories(eng, run_kw, map_final):
     return hist
 
 
+def payoff_option_values(values):
+    """(BatchEngine.run's payoff keyword arguments, payoff_map_final) from option values (a mapping;
+    absent: default)."""
+    every, max_d, final = (conv(values.get(name, default)) for name, (default, conv) in PAYOFF_OPTIONS.items())
+    if (final or max_d is not None) and not every:
+        raise ValueError("payoff_max_distance and payoff_map_final need payoff_history_every > 0 (nothing is "
+                         "recorded otherwise)")
+    return dict(payoff_every=every, payoff_max_d=max_d), final
+
+
+def payoff_histories(eng, run_kw, map_final):
+    """write_datasets' payoff_hist of every replica of a run(**run_kw): the engine's payoff_histories,
+    with map_final also the final state's map; None without the record."""
+    if not run_kw["payoff_every"]:
+        return None
+    hist = eng.payoff_histories()
+    if map_final:
+        for k, h in enumerate(hist):
+            h[PAYOFF_MAP_DATASET] = eng.payoff_map(k)
+    return hist
+
+
 def record_run_kwargs(values):
     """BatchEngine.run's record keyword arguments from option values (a mapping; absent: default)."""
     return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in RECORD_OPTIONS.items()}
@@ -152,8 +189,8 @@ class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
-    # (the RECORD_OPTIONS, DWELL_OPTIONS, CLUSTER_TILED_OPTIONS and POLICY_OPTIONS are class attributes too, set at their defaults
-    # below the class)
+    # (the RECORD_OPTIONS, DWELL_OPTIONS, CLUSTER_TILED_OPTIONS, POLICY_OPTIONS and PAYOFF_OPTIONS are class attributes too, set
+    # at their defaults below the class)
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -264,12 +301,15 @@ class SPGG:
             dwell_every, dwell_fields = dwell_option_values({name: getattr(self, name) for name in DWELL_OPTIONS})
             tiled = cluster_tiled_run_kwargs({name: getattr(self, name) for name in CLUSTER_TILED_OPTIONS})
             policy_kw, policy_map = policy_option_values({name: getattr(self, name) for name in POLICY_OPTIONS})
-            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records, **tiled, **policy_kw)
+            payoff_kw, payoff_map = payoff_option_values({name: getattr(self, name) for name in PAYOFF_OPTIONS})
+            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records, **tiled, **policy_kw,
+                    **payoff_kw)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (over many workgroups above side 200)
             record_hists = {arg: h and h[0] for arg, h in record_histories(eng, records).items()}
             dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
             policy_hist = policy_histories(eng, policy_kw, policy_map)
+            payoff_hist = payoff_histories(eng, payoff_kw, payoff_map)
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -301,7 +341,8 @@ class SPGG:
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
                        clusters=clusters, dwell_hist=dwell_hist and dwell_hist[0],
-                       policy_hist=policy_hist and policy_hist[0], **record_hists)
+                       policy_hist=policy_hist and policy_hist[0], payoff_hist=payoff_hist and payoff_hist[0],
+                       **record_hists)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -315,6 +356,8 @@ for _name, (_default, _conv) in DWELL_OPTIONS.items():
 for _name, (_default, _kw, _conv) in CLUSTER_TILED_OPTIONS.items():
     setattr(SPGG, _name, _default)
 for _name, (_default, _conv) in POLICY_OPTIONS.items():
+    setattr(SPGG, _name, _default)
+for _name, (_default, _conv) in PAYOFF_OPTIONS.items():
     setattr(SPGG, _name, _default)
 
 
@@ -353,7 +396,8 @@ def record_histories(eng, run_kwargs):
 
 
 def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
-                   cluster_hist=None, correlation_hist=None, reputation_hist=None, dwell_hist=None, policy_hist=None):
+                   cluster_hist=None, correlation_hist=None, reputation_hist=None, dwell_hist=None, policy_hist=None,
+                   payoff_hist=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
     the final state.  Shared by SPGG.run and the batched sweep runner.
@@ -367,7 +411,9 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
     (BatchEngine.dwell_histories), written as the DWELL_DATASETS after those, then the
     DWELL_FIELD_DATASETS it holds (int64; cooperation_frequency_final f64); policy_hist: the in-run
     policy record (BatchEngine.policy_histories), written as the POLICY_DATASETS after those (int64;
-    policy_gap_bin_edges f64), then POLICY_MAP_DATASET (uint8) if it holds it.
+    policy_gap_bin_edges f64), then POLICY_MAP_DATASET (uint8) if it holds it; payoff_hist: the in-run
+    payoff record (BatchEngine.payoff_histories), written as the PAYOFF_DATASETS after those (int64;
+    payoff_values f64), then PAYOFF_PAIRS_DATASET (int64) and PAYOFF_MAP_DATASET (uint8) if it holds them.
     The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
@@ -414,6 +460,13 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
                 policy_hist[name], dtype=np.float64 if name == "policy_gap_bin_edges" else np.int64))
         if policy_hist is not None and POLICY_MAP_DATASET in policy_hist:
             data_file.create_dataset(POLICY_MAP_DATASET, data=np.asarray(policy_hist[POLICY_MAP_DATASET], dtype=np.uint8))
+        for name in PAYOFF_DATASETS if payoff_hist is not None else ():
+            data_file.create_dataset(name, data=np.asarray(
+                payoff_hist[name], dtype=np.float64 if name == "payoff_values" else np.int64))
+        if payoff_hist is not None and PAYOFF_PAIRS_DATASET in payoff_hist:
+            data_file.create_dataset(PAYOFF_PAIRS_DATASET, data=np.asarray(payoff_hist[PAYOFF_PAIRS_DATASET], dtype=np.int64))
+        if payoff_hist is not None and PAYOFF_MAP_DATASET in payoff_hist:
+            data_file.create_dataset(PAYOFF_MAP_DATASET, data=np.asarray(payoff_hist[PAYOFF_MAP_DATASET], dtype=np.uint8))
 
 
 def track_positions(L):

@@ -1,6 +1,6 @@
-"""What the device records cost (profiles/{clusters,correlations,reputation,dwell,policy}/README.txt).
+"""What the device records cost (profiles/{clusters,correlations,reputation,dwell,policy,payoff}/README.txt).
 
-    python tools/record_cost.py --record clusters|correlations|reputation|dwell|policy [--repeats 5] [--iters 10000]
+    python tools/record_cost.py --record clusters|correlations|reputation|dwell|policy|payoff [--repeats 5] [--iters 10000]
                                 [--legs LEG,LEG,...]
 
 Every variant runs in a fresh process (this driver never touches the GPU) and reports the median of
@@ -38,6 +38,13 @@ its repeats.  Legs (default: all of the record's, in this order):
                        fraction of the byte floor at 8 TB/s; variant CONFIG:pending|flushed
                 run    the whole run (BatchEngine.run, MT19937) of cfg3, cfg4 and cfg5 with policy_every
                        0 / 100 / 10 / 1; variant CONFIG:EVERY:ITERATIONS
+  payoff        census device time of one spgg_payoff_census round (two launches: zero, census with the plane)
+                       at cfg3's, cfg4's and cfg5's shapes after 200 iterations; the fraction of the byte floor
+                       (1 B read, 1 B written per agent) at 8 TB/s
+                pairs  the same for one spgg_payoff_pairs round on the plane that census wrote, max_d as for
+                       correlations
+                run    the whole run (BatchEngine.run, MT19937) of cfg3, cfg4 and cfg5 with payoff_every
+                       0 / 100 / 10 / 1 (max_d as above where armed); variant CONFIG:EVERY:ITERATIONS
   every other   run    the whole cfg3 run (BatchEngine.run, MT19937, as bench.full_run times it) with
                        the record every {0, 16, 1} iterations (max_d = 100, 20 bins)
 """
@@ -416,6 +423,65 @@ def leg_policy_run(a):
             "us_per_iter": [s / executed * 1e6 for s in out[1:]], "seconds": out[1:]}
 
 
+def leg_payoff_call(a):
+    import torch
+    from spgg_amd.payoff import PAYOFF_SLOTS, pairs_width
+    config = a.variant
+    D = MAX_D[config]
+    eng = _engine_at(config, 200, 300)
+    try:
+        plane = eng._payoff_plane()
+        census = torch.zeros((eng.R, PAYOFF_SLOTS), dtype=torch.int32, device=eng.dev)
+
+        def census_call(g, s):
+            return eng.lib.spgg_payoff_census(g["ctx"], eng.t, plane[g["r0"]].data_ptr(), census[g["r0"]].data_ptr(),
+                                              PAYOFF_SLOTS, s)
+        info = {"L": eng.L, "replicas": eng.R, "groups": eng.G}
+        if a.child == "census":
+            us = _timed_rounds(eng, a, census_call)
+            bytes_ = 2 * eng.R * eng.n
+        else:
+            for g in eng.groups:
+                assert census_call(g, torch.cuda.current_stream(eng.dev).cuda_stream) == 0
+            width = pairs_width(D)
+            out_buf = torch.zeros((eng.R, width), dtype=torch.int64, device=eng.dev)
+            us = _timed_rounds(eng, a, lambda g, s: eng.lib.spgg_payoff_pairs(
+                g["ctx"], eng.t, D, plane[g["r0"]].data_ptr(), out_buf[g["r0"]].data_ptr(), width, s))
+            got = out_buf.cpu().numpy()[:, 2:].reshape(eng.R, 2, D + 1, 3)
+            assert (got[:, 0, 0] == got[:, 1, 0]).all()   # rows[0] == cols[0]
+            bytes_ = eng.R * eng.n * 2 * (D + 1)           # the plane once per (direction, distance)
+            info["max_d"] = D
+        got = census.cpu().numpy()
+        assert (got[:, :260].sum(axis=1) == eng.n).all() and (got[:, 260:].sum(axis=1) == 2 * eng.n).all()
+        floor_us = bytes_ / FLOOR_BYTES_PER_SECOND * 1e6
+        return {"leg": a.child, "variant": a.variant, **info, "MB": round(bytes_ / 1e6, 1), "floor_us": round(floor_us, 2),
+                "floor_fraction": [round(floor_us / u, 3) for u in us], "us_per_round": us}
+    finally:
+        eng.close()
+
+
+def leg_payoff_run(a):
+    import torch
+    import bench
+    from spgg_amd.engine import BatchEngine
+    config, every, iters = a.variant.split(":")
+    _desc, L, M2, state, reps = bench.workload(config, 0)
+    out = []
+    for _ in range(a.repeats + 1):
+        eng = BatchEngine(L, int(iters), reps, use_second_order=M2, state_representation=state, rng="mt19937")
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.run(snapshots=False, payoff_every=int(every), payoff_max_d=MAX_D[config] if int(every) else None)
+            torch.cuda.synchronize()
+            out.append(time.perf_counter() - t0)
+            executed = eng.t - 1
+        finally:
+            eng.close()
+    return {"leg": "run", "variant": a.variant, "iterations": executed, "replicas": len(reps), "L": L,
+            "us_per_iter": [s / executed * 1e6 for s in out[1:]], "seconds": out[1:]}
+
+
 RUN = (leg_run, ["0", "16", "1"])
 LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
                      "call": (leg_call, [f"{c}:{s}:{p}" for c in ("cfg3", "cfg4") for s in ("record", "sizes")
@@ -431,7 +497,9 @@ LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
                   "launch": (leg_dwell_launch, [f"{c}:{t}" for c in SHAPES for t in (20, 400)]),
                   "record": (leg_dwell_record, [f"{c}:{w}" for c in SHAPES for w in ("record", "fields")])},
         "policy": {"call": (leg_policy_call, [f"{c}:{w}" for c in SHAPES for w in ("pending", "flushed")]),
-                   "run": (leg_policy_run, [f"{c}:{e}:iters" for c in SHAPES for e in (0, 100, 10, 1)])}}
+                   "run": (leg_policy_run, [f"{c}:{e}:iters" for c in SHAPES for e in (0, 100, 10, 1)])},
+        "payoff": {"census": (leg_payoff_call, SHAPES), "pairs": (leg_payoff_call, SHAPES),
+                   "run": (leg_payoff_run, [f"{c}:{e}:iters" for c in SHAPES for e in (0, 100, 10, 1)])}}
 
 
 def main():
@@ -447,7 +515,7 @@ def main():
     if a.child:
         print("RESULT " + json.dumps(legs[a.child][0](a)), flush=True)
         return 0
-    width = 16 if a.record in ("clusters", "dwell", "policy") else 6
+    width = 16 if a.record in ("clusters", "dwell", "policy", "payoff") else 6
     for leg in (a.legs.split(",") if a.legs else legs):
         for variant in legs[leg][1]:
             variant = variant.replace(":iters", f":{a.iters}")
