@@ -47,6 +47,10 @@ POLICY_COUNTS = 21   # SPGG_POLICY_COUNTS
 # bond_dd[|dK|] (26 each)
 PAYOFF_SLOTS, PAYOFF_BOND_CD, PAYOFF_BOND_CC, PAYOFF_BOND_DD = 363, 260, 311, 337
 
+# pair map (spgg_abi.h): the field table and the cap on a call's work, in word blocks
+FIELD_COOP, FIELD_FLIP = 0, 1
+PAIR_MAP_WORK_CAP = 87_000_000_000   # SPGG_PAIR_MAP_WORK_CAP
+
 EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create", "spgg_set_params",
             "spgg_bind", "spgg_step", "spgg_step_groups", "spgg_flush", "spgg_draw", "spgg_payoff", "spgg_tile_shape",
             "spgg_destroy", "spgg_draw_planes", "spgg_pub_doubles", "spgg_stat_stripes",
@@ -56,7 +60,8 @@ EXPORTED = ("spgg_abi_version", "spgg_build_id", "spgg_last_error", "spgg_create
             "spgg_correlations", "spgg_correlations_max_side", "spgg_reputation_hist",
             "spgg_reputation_pairs", "spgg_reputation_max_side", "spgg_dwell_bind", "spgg_dwell_reset",
             "spgg_dwell_record", "spgg_dwell_fields", "spgg_clusters_tiled", "spgg_clusters_tiled_workspace",
-            "spgg_policy", "spgg_payoff_census", "spgg_payoff_pairs", "spgg_payoff_pairs_max_side")
+            "spgg_policy", "spgg_payoff_census", "spgg_payoff_pairs", "spgg_payoff_pairs_max_side",
+            "spgg_pair_map_work", "spgg_pair_map_workspace", "spgg_pair_map")
 # test-only entry points (include/spgg_test.h): exported by the library, not part of the product ABI
 TEST_EXPORTED = ("spgg_test_set_error",)
 
@@ -170,6 +175,12 @@ def load(path: str | None = None):
         lib.spgg_payoff_pairs.argtypes = [vp, i32, i32, vp, vp, ctypes.c_int64, vp]
         lib.spgg_payoff_pairs_max_side.restype = ctypes.c_int
         lib.spgg_payoff_pairs_max_side.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.spgg_pair_map_work.restype = ctypes.c_int
+        lib.spgg_pair_map_work.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+        lib.spgg_pair_map_workspace.restype = ctypes.c_int
+        lib.spgg_pair_map_workspace.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int64)]
+        lib.spgg_pair_map.restype = ctypes.c_int
+        lib.spgg_pair_map.argtypes = [vp, i32, i32, i32, i32, vp, vp, ctypes.c_int64, vp]
         lib.spgg_persistent.restype = ctypes.c_int
         lib.spgg_persistent.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         lib.spgg_destroy.restype = ctypes.c_int

@@ -29,7 +29,8 @@ UNITS += [(os.path.join(CSRC, f"spgg_{name}.hip"), (), f"{name}.o")
                        "dwell",            # strategy dwell record
                        "clusters_tiled",   # cluster labelling over many workgroups
                        "policy",           # learned policy record
-                       "payoff")]          # payoff record
+                       "payoff",           # payoff record
+                       "pair_map")]        # 2-D pair maps of strategies and flips
 SRC = list(dict.fromkeys(u[0] for u in UNITS))  # the distinct source files
 INC = os.path.join(ROOT, "include")
 OUT = os.path.join(PKG_DIR, "libspgg_hip.so")

@@ -52,6 +52,7 @@
 #include "spgg_correlations.h"
 #include "spgg_reputation.h"
 #include "spgg_dwell.h"
+#include "spgg_pair_map.h"
 #include "spgg_payoff.h"
 #include "spgg_policy.h"
 
@@ -3347,6 +3348,36 @@ int spgg_payoff_pairs(spgg_ctx* c, int32_t t, int32_t max_d, const uint8_t* plan
   spgg_pf::launch_pairs(lattices(c), max_d, plane, reinterpret_cast<long long*>(out), out_stride,
                         reinterpret_cast<hipStream_t>(stream));
   return hip_check(c, hipGetLastError(), "spgg_payoff_pairs launch");
+}
+
+int spgg_pair_map_work(int32_t L, int32_t n_rep, int32_t max_d, int64_t* work, int64_t* cap) {
+  if (!work || !cap || L < 1 || n_rep < 1 || max_d < 0 || max_d > L / 2) return SPGG_E_ARG;
+  *work = spgg_pm::work(L, n_rep, max_d);
+  *cap = spgg_pm::kWorkCap;
+  return SPGG_OK;
+}
+
+int spgg_pair_map_workspace(const spgg_ctx* c, int32_t max_d, int64_t* words_per_rep) {
+  if (!c || !words_per_rep || max_d < 0 || max_d > c->cfg.L / 2) return SPGG_E_ARG;
+  *words_per_rep = spgg_pm::plane_words(c->cfg.L, max_d);
+  return SPGG_OK;
+}
+
+int spgg_pair_map(spgg_ctx* c, int32_t t, int32_t field_a, int32_t field_b, int32_t max_d, uint32_t* work, int32_t* out,
+                  int64_t out_stride, void* stream) {
+  if (const int rc = observable_check(c, "spgg_pair_map", work && out, false, t)) return rc;
+  if (field_a < 0 || field_a >= spgg_pm::kFields || field_b < 0 || field_b >= spgg_pm::kFields)
+    return fail(c, SPGG_E_ARG, "spgg_pair_map: fields (" + std::to_string(field_a) + ", " + std::to_string(field_b) +
+                                   ") outside the table 0 .. " + std::to_string(spgg_pm::kFields - 1));
+  if (const int rc = range_check(c, "spgg_pair_map", INT32_MAX, "none", max_d)) return rc;
+  if (out_stride < spgg_pm::map_width(max_d))
+    return fail(c, SPGG_E_ARG, "spgg_pair_map: out_stride below (max_d + 1) * (2 * max_d + 1)");
+  const int64_t w = spgg_pm::work(c->cfg.L, c->cfg.n_rep, max_d);
+  if (w > spgg_pm::kWorkCap)
+    return fail(c, SPGG_E_ARG, "spgg_pair_map: work " + std::to_string(w) + " word blocks above the cap " +
+                                   std::to_string(spgg_pm::kWorkCap) + " (spgg_pair_map_work; a smaller max_d)");
+  spgg_pm::launch(lattices(c), t, field_a, field_b, max_d, work, out, out_stride, reinterpret_cast<hipStream_t>(stream));
+  return hip_check(c, hipGetLastError(), "spgg_pair_map launch");
 }
 
 int spgg_status(const spgg_ctx* c, uint32_t* flags) {

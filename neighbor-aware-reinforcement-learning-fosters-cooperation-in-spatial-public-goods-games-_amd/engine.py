@@ -33,6 +33,7 @@ import torch
 from . import _lib as C
 from .algorithms import canonical_name
 from .dwell import DWELL_SLOTS, Dwell
+from . import pairmap
 from .payoff import PAYOFF_SLOTS, Payoff, pairs_width
 from .policy import Policy, policy_bin_edges, policy_width, split_row
 from .records import (KINDS, next_boundary, clusters_cap_text,  # noqa: F401  (the host models stay importable from here)
@@ -337,6 +338,7 @@ class BatchEngine:
         self._clusters_work = None   # the workspace of spgg_clusters_tiled, allocated on first use
         self._policy_work = None     # the (R, n) uint8 plane of spgg_policy, allocated on first use
         self._payoff_work = None     # the (R, n) uint8 plane of spgg_payoff_census, allocated on first use
+        self._pair_map_ws = None     # the (R, words) workspace of spgg_pair_map (the packed planes), allocated on first use
 
     def state_bytes_per_replica(self) -> int:
         """Bytes of per-agent state one iteration reads and writes (Q, the S / R ping-pong,
@@ -710,7 +712,8 @@ class BatchEngine:
             correlations_max_d: Optional[int] = None, reputation_every: int = 0,
             reputation_bins: int = 20, reputation_max_d: Optional[int] = None, dwell_every: int = 0,
             clusters_tiled=False, policy_every: int = 0, policy_bins: int = 32, policy_gap_range=2.0,
-            payoff_every: int = 0, payoff_max_d: Optional[int] = None):
+            payoff_every: int = 0, payoff_max_d: Optional[int] = None, pair_map_every: int = 0,
+            pair_map_max_d: Optional[int] = None, pair_map_fields=(("coop", "coop"),)):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -758,9 +761,19 @@ class BatchEngine:
         difference in K; with payoff_max_d also spgg_payoff_pairs, the pair sums of K and c at the
         distances 0 .. payoff_max_d) on the same schedule; read with payoff_histories().  Settings as
         for the other records; a function of S_t alone, so allowed on an engine that steps in
+        persistent launches.
+        pair_map_every = k > 0 records 2-D pair maps of S_t (spgg_pair_map, pairmap.py: for every displacement
+        (dx, dy), dy = 0 .. D, dx = -D .. D, the cells with field a set whose partner has field b set) on
+        the same schedule, one map per (a, b) of pair_map_fields -- a tuple of distinct pairs of "coop"
+        (the cooperators) and "flip" (the agents that changed strategy in iteration t - 1); D =
+        pair_map_max_d, None: min(L // 2, 32).  A row holds (D + 1)(2 D + 1) int32 per replica and pair:
+        4 (D + 1)(2 D + 1) bytes, 8,580 at D = 32 and 81,204 at D = 100.  A distance whose call would exceed
+        the work cap (pairmap.work, pairmap.WORK_CAP) is refused; read with pair_map_histories().  Settings
+        as for the other records; a function of S_t alone, so allowed on an engine that steps in
         persistent launches."""
         policy_key = Policy.validate(self, policy_every, policy_bins, policy_gap_range)   # (before any allocation)
         payoff_key = Payoff.validate(self, payoff_every, payoff_max_d)
+        pair_map_key = pairmap.PairMap.validate(self, pair_map_every, pair_map_max_d, pair_map_fields)
         asked = {"clusters": (clusters_every, clusters_periodic, clusters_tiled), "correlations": (correlations_every, correlations_max_d),
                  "reputation": (reputation_every, reputation_bins, reputation_max_d)}
         keys = {name: KINDS[name].validate(self, *a) for name, a in asked.items()}   # (before any allocation)
@@ -790,6 +803,8 @@ class BatchEngine:
             active.append(rec)
         if payoff_key[0]:
             active.append(self._record("payoff", payoff_key, Payoff))
+        if pair_map_key[0]:
+            active.append(self._record("pair_map", pair_map_key, pairmap.PairMap))
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -1213,6 +1228,38 @@ class BatchEngine:
         (m, 2, 5, 26), payoff_bond_history (m, 103: bond_cd, bond_cc, bond_dd) and payoff_values f64
         (2, 26); with payoff_max_d also payoff_pair_sums_history (m, 2 + 6 (D + 1))."""
         return self._histories("payoff", "payoff_histories: run(payoff_every=k)")
+
+    # -- the pair maps (pairmap.py; spgg_pair_map) ---------------------------------------------
+    def _pair_map_work(self, D):
+        """The (R, words) int32 workspace of spgg_pair_map (the two bit-packed planes of each replica),
+        allocated on first use for the distance asked for; a larger distance later takes a new one (a
+        record keeps the one it was planned with)."""
+        words = ctypes.c_int64(0)
+        C.check(self.lib.spgg_pair_map_workspace(self.ctx, int(D), ctypes.byref(words)), self.ctx, "spgg_pair_map_workspace")
+        if self._pair_map_ws is None or self._pair_map_ws.shape[1] < int(words.value):
+            self._pair_map_ws = torch.empty((self.R, int(words.value)), dtype=torch.int32, device=self.dev)
+        return self._pair_map_ws
+
+    def pair_map(self, k, a: str = "coop", b: str = "coop", max_d: Optional[int] = None) -> np.ndarray:
+        """int64 (D + 1, 2 D + 1) pair map of replica k in the state the engine is in (after run():
+        final_state(k)'s), D = max_d (None: L // 2): [dy, dx + D] the cells with field a set whose partner
+        (dx, dy) away on the periodic lattice has field b set; a, b: "coop" (the cooperators) or "flip"
+        (the agents that changed strategy in the last iteration).  Counted on the device, all replicas
+        at once (one spgg_pair_map call per replica group), and cached until the engine steps again.
+        pairmap.full_plane / radial_function / structure_factor turn maps into the whole plane, G(r) and S(k)."""
+        (a, b), = pairmap.field_pairs(((a, b),))
+        D = self.L // 2 if max_d is None else int(max_d)
+        _, D, _ = pairmap.PairMap.validate(self, 1, D, ((a, b),), "pair_map")
+        shape = pairmap.map_shape(D)
+        out = self._final(("pair_map", a, b, D), self.lib.spgg_pair_map,
+                          (pairmap.FIELDS[a], pairmap.FIELDS[b], D, self._pair_map_work(D)), shape[0] * shape[1])
+        return out[k].reshape(shape).copy()
+
+    def pair_map_histories(self):
+        """Per replica, the in-run pair-map record of run(pair_map_every=k): pair_map_history_iters (the
+        recorded iterations t <= last_iteration), one pair_map_<a>_<b>_history int64 (m, D + 1, 2 D + 1) per
+        field pair, and pair_map_max_distance (D)."""
+        return self._histories("pair_map", "pair_map_histories: run(pair_map_every=k)")
 
     def finalize_history(self):
         """Derived history slots (payoff sums, w_P*P, w_rep*rr, reward over D) of every

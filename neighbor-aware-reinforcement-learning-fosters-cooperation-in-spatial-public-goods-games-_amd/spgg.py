@@ -18,6 +18,7 @@ from . import algorithms as A
 from .dwell import DWELL_DATASETS, DWELL_FIELD_DATASETS
 from .engine import BatchEngine, InitState, ReplicaParams, SNAPSHOT_ITERS
 from .h5io import open_writer
+from .pairmap import PAIR_MAP_DISTANCE_DATASET, PAIR_MAP_ITERS_DATASET, field_pairs
 from .payoff import PAYOFF_DATASETS, PAYOFF_MAP_DATASET, PAYOFF_PAIRS_DATASET
 from .policy import POLICY_DATASETS, POLICY_MAP_DATASET
 
@@ -93,6 +94,19 @@ PAYOFF_OPTIONS = {
     "payoff_history_every": (0, _count),
     "payoff_max_distance": (None, lambda v: v),
     "payoff_map_final": (False, bool),
+}
+
+
+# The pair-map record's options (pairmap.py), class attributes of SPGG in a table of their own as the
+# payoff record's are.  name -> (default, conversion).  pair_map_history_every = k > 0: record the 2-D pair
+# maps of the fields of pair_map_fields -- a tuple of (a, b) pairs of "coop" and "flip" -- at every
+# displacement up to pair_map_max_distance (None: min(L // 2, 32)) at t = 1, 1+k, ... on the device and
+# write pair_map_history_iters, one pair_map_<a>_<b>_history per pair and pair_map_max_distance after the
+# payoff datasets.
+PAIR_MAP_OPTIONS = {
+    "pair_map_history_every": (0, _count),
+    "pair_map_max_distance": (None, lambda v: v),
+    "pair_map_fields": ((("coop", "coop"),), lambda v: tuple(tuple(p) for p in v)),
 }
 
 
@@ -180,6 +194,20 @@ def payoff_histories(eng, run_kw, map_final):
     return hist
 
 
+def pair_map_option_values(values):
+    """BatchEngine.run's pair-map keyword arguments from option values (a mapping; absent: default)."""
+    every, max_d, fields = (conv(values.get(name, default)) for name, (default, conv) in PAIR_MAP_OPTIONS.items())
+    if max_d is not None and not every:
+        raise ValueError("pair_map_max_distance needs pair_map_history_every > 0 (nothing is recorded otherwise)")
+    return dict(pair_map_every=every, pair_map_max_d=max_d, pair_map_fields=field_pairs(fields))
+
+
+def pair_map_histories(eng, run_kw):
+    """write_datasets' pair_map_hist of every replica of a run(**run_kw): the engine's pair_map_histories;
+    None without the record."""
+    return eng.pair_map_histories() if run_kw["pair_map_every"] else None
+
+
 def record_run_kwargs(values):
     """BatchEngine.run's record keyword arguments from option values (a mapping; absent: default)."""
     return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in RECORD_OPTIONS.items()}
@@ -189,7 +217,7 @@ class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
-    # (the RECORD_OPTIONS, DWELL_OPTIONS, CLUSTER_TILED_OPTIONS, POLICY_OPTIONS and PAYOFF_OPTIONS are class attributes too, set
+    # (the RECORD_OPTIONS, DWELL_OPTIONS, CLUSTER_TILED_OPTIONS, POLICY_OPTIONS, PAYOFF_OPTIONS and PAIR_MAP_OPTIONS are class attributes too, set
     # at their defaults below the class)
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
@@ -302,14 +330,16 @@ class SPGG:
             tiled = cluster_tiled_run_kwargs({name: getattr(self, name) for name in CLUSTER_TILED_OPTIONS})
             policy_kw, policy_map = policy_option_values({name: getattr(self, name) for name in POLICY_OPTIONS})
             payoff_kw, payoff_map = payoff_option_values({name: getattr(self, name) for name in PAYOFF_OPTIONS})
+            pair_map_kw = pair_map_option_values({name: getattr(self, name) for name in PAIR_MAP_OPTIONS})
             eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records, **tiled, **policy_kw,
-                    **payoff_kw)
+                    **payoff_kw, **pair_map_kw)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (over many workgroups above side 200)
             record_hists = {arg: h and h[0] for arg, h in record_histories(eng, records).items()}
             dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
             policy_hist = policy_histories(eng, policy_kw, policy_map)
             payoff_hist = payoff_histories(eng, payoff_kw, payoff_map)
+            pair_map_hist = pair_map_histories(eng, pair_map_kw)
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -342,7 +372,7 @@ class SPGG:
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
                        clusters=clusters, dwell_hist=dwell_hist and dwell_hist[0],
                        policy_hist=policy_hist and policy_hist[0], payoff_hist=payoff_hist and payoff_hist[0],
-                       **record_hists)
+                       pair_map_hist=pair_map_hist and pair_map_hist[0], **record_hists)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -358,6 +388,8 @@ for _name, (_default, _kw, _conv) in CLUSTER_TILED_OPTIONS.items():
 for _name, (_default, _conv) in POLICY_OPTIONS.items():
     setattr(SPGG, _name, _default)
 for _name, (_default, _conv) in PAYOFF_OPTIONS.items():
+    setattr(SPGG, _name, _default)
+for _name, (_default, _conv) in PAIR_MAP_OPTIONS.items():
     setattr(SPGG, _name, _default)
 
 
@@ -397,7 +429,7 @@ def record_histories(eng, run_kwargs):
 
 def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
                    cluster_hist=None, correlation_hist=None, reputation_hist=None, dwell_hist=None, policy_hist=None,
-                   payoff_hist=None):
+                   payoff_hist=None, pair_map_hist=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
     the final state.  Shared by SPGG.run and the batched sweep runner.
@@ -413,7 +445,10 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
     policy record (BatchEngine.policy_histories), written as the POLICY_DATASETS after those (int64;
     policy_gap_bin_edges f64), then POLICY_MAP_DATASET (uint8) if it holds it; payoff_hist: the in-run
     payoff record (BatchEngine.payoff_histories), written as the PAYOFF_DATASETS after those (int64;
-    payoff_values f64), then PAYOFF_PAIRS_DATASET (int64) and PAYOFF_MAP_DATASET (uint8) if it holds them.
+    payoff_values f64), then PAYOFF_PAIRS_DATASET (int64) and PAYOFF_MAP_DATASET (uint8) if it holds them;
+    pair_map_hist: the in-run pair-map record (BatchEngine.pair_map_histories), written after those:
+    pair_map_history_iters, one pair_map_<a>_<b>_history (rows, D + 1, 2 D + 1) per field pair and the scalar
+    pair_map_max_distance, all int64.
     The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
@@ -467,6 +502,10 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
             data_file.create_dataset(PAYOFF_PAIRS_DATASET, data=np.asarray(payoff_hist[PAYOFF_PAIRS_DATASET], dtype=np.int64))
         if payoff_hist is not None and PAYOFF_MAP_DATASET in payoff_hist:
             data_file.create_dataset(PAYOFF_MAP_DATASET, data=np.asarray(payoff_hist[PAYOFF_MAP_DATASET], dtype=np.uint8))
+        if pair_map_hist is not None:
+            maps = [name for name in pair_map_hist if name not in (PAIR_MAP_ITERS_DATASET, PAIR_MAP_DISTANCE_DATASET)]
+            for name in [PAIR_MAP_ITERS_DATASET, *maps, PAIR_MAP_DISTANCE_DATASET]:
+                data_file.create_dataset(name, data=np.asarray(pair_map_hist[name], dtype=np.int64))
 
 
 def track_positions(L):

@@ -1,6 +1,6 @@
-"""What the device records cost (profiles/{clusters,correlations,reputation,dwell,policy,payoff}/README.txt).
+"""What the device records cost (profiles/{clusters,correlations,reputation,dwell,policy,payoff,pair_map}/README.txt).
 
-    python tools/record_cost.py --record clusters|correlations|reputation|dwell|policy|payoff [--repeats 5] [--iters 10000]
+    python tools/record_cost.py --record clusters|correlations|reputation|dwell|policy|payoff|pair_map [--repeats 5] [--iters 10000]
                                 [--legs LEG,LEG,...]
 
 Every variant runs in a fresh process (this driver never touches the GPU) and reports the median of
@@ -45,6 +45,14 @@ its repeats.  Legs (default: all of the record's, in this order):
                        correlations
                 run    the whole run (BatchEngine.run, MT19937) of cfg3, cfg4 and cfg5 with payoff_every
                        0 / 100 / 10 / 1 (max_d as above where armed); variant CONFIG:EVERY:ITERATIONS
+  pair_map      call   device time of one spgg_pair_map round (two launches: pack, count) at cfg3's, cfg4's and
+                       cfg5's shapes after 200 iterations, at D = 32 and D = L // 2, for the cooperator auto-map
+                       alone (cc) and for cc + ff + cf; the work in word blocks and the rate; variant
+                       CONFIG:D:cc|all
+                run    the whole cfg3 run (BatchEngine.run, MT19937) with pair_map_every 0 / 100 / 10 at D = 32;
+                       variant cfg3:EVERY:ITERATIONS
+                host   the same maps by pairmap.host_pair_map (np.roll) on host copies of the planes, the copy
+                       included, at D = 32, and by pairmap.host_pair_map_fft at D = L // 2; variant CONFIG:D:roll|fft
   every other   run    the whole cfg3 run (BatchEngine.run, MT19937, as bench.full_run times it) with
                        the record every {0, 16, 1} iterations (max_d = 100, 20 bins)
 """
@@ -482,6 +490,83 @@ def leg_payoff_run(a):
             "us_per_iter": [s / executed * 1e6 for s in out[1:]], "seconds": out[1:]}
 
 
+PAIR_MAP_FIELDS = {"cc": (("coop", "coop"),), "all": (("coop", "coop"), ("flip", "flip"), ("coop", "flip"))}
+
+
+def leg_pair_map_call(a):
+    import torch
+    from spgg_amd import pairmap
+    config, D, which = a.variant.split(":")
+    eng = _engine_at(config, 200, 300, flush=False)
+    try:
+        D = eng.L // 2 if D == "half" else int(D)
+        pairs = [(pairmap.FIELDS[x], pairmap.FIELDS[y]) for x, y in PAIR_MAP_FIELDS[which]]
+        shape = pairmap.map_shape(D)
+        width = shape[0] * shape[1]
+        ws = eng._pair_map_work(D)
+        outs = [torch.zeros((eng.R, width), dtype=torch.int32, device=eng.dev) for _ in pairs]
+
+        def call(g, s):
+            rc = 0
+            for (fa, fb), o in zip(pairs, outs):
+                rc = rc or eng.lib.spgg_pair_map(g["ctx"], eng.t, fa, fb, D, ws[g["r0"]].data_ptr(), o[g["r0"]].data_ptr(), width, s)
+            return rc
+        us = _timed_rounds(eng, a, call)
+        cc = outs[0].cpu().numpy().reshape((eng.R,) + shape)
+        assert (cc[:, 0, D + 1:] == cc[:, 0, D - 1::-1][:, :D]).all() if D else True      # the axis row is symmetric
+        work = sum(pairmap.work(eng.L, g["r1"] - g["r0"], D) for g in eng.groups) * len(pairs)
+        return {"leg": "call", "variant": a.variant, "L": eng.L, "replicas": eng.R, "groups": eng.G, "max_d": D,
+                "maps": len(pairs), "word_blocks": work, "word_blocks_per_second": [round(work / (u * 1e-6)) for u in us],
+                "us_per_round": us}
+    finally:
+        eng.close()
+
+
+def leg_pair_map_run(a):
+    import torch
+    import bench
+    from spgg_amd.engine import BatchEngine
+    config, every, iters = a.variant.split(":")
+    _desc, L, M2, state, reps = bench.workload(config, 0)
+    out = []
+    for _ in range(a.repeats + 1):
+        eng = BatchEngine(L, int(iters), reps, use_second_order=M2, state_representation=state, rng="mt19937")
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.run(snapshots=False, pair_map_every=int(every), pair_map_max_d=32 if int(every) else None)
+            torch.cuda.synchronize()
+            out.append(time.perf_counter() - t0)
+            executed = eng.t - 1
+        finally:
+            eng.close()
+    return {"leg": "run", "variant": a.variant, "iterations": executed, "replicas": len(reps), "L": L,
+            "us_per_iter": [s / executed * 1e6 for s in out[1:]], "seconds": out[1:]}
+
+
+def leg_pair_map_host(a):
+    from spgg_amd import pairmap
+    config, D, how = a.variant.split(":")
+    eng = _engine_at(config, 200, 300)
+    try:
+        D = eng.L // 2 if D == "half" else int(D)
+        fn = pairmap.host_pair_map if how == "roll" else pairmap.host_pair_map_fft
+        device = [eng.pair_map(k, "coop", "coop", D) for k in range(eng.R)]
+        out = []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            host = []
+            for S in _final_planes(eng, eng.S):          # (the copy is part of the host path)
+                c = (S & 1) == 0
+                host.append(fn(c, c, D))
+            out.append(time.perf_counter() - t0)
+        same = all((h == d).all() for h, d in zip(host, device))
+        return {"leg": "host", "variant": a.variant, "L": eng.L, "max_d": D, "replicas": eng.R, "equals_device": bool(same),
+                "seconds": out}
+    finally:
+        eng.close()
+
+
 RUN = (leg_run, ["0", "16", "1"])
 LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
                      "call": (leg_call, [f"{c}:{s}:{p}" for c in ("cfg3", "cfg4") for s in ("record", "sizes")
@@ -499,7 +584,11 @@ LEGS = {"clusters": {"final": (leg_final, ["device", "host"]),
         "policy": {"call": (leg_policy_call, [f"{c}:{w}" for c in SHAPES for w in ("pending", "flushed")]),
                    "run": (leg_policy_run, [f"{c}:{e}:iters" for c in SHAPES for e in (0, 100, 10, 1)])},
         "payoff": {"census": (leg_payoff_call, SHAPES), "pairs": (leg_payoff_call, SHAPES),
-                   "run": (leg_payoff_run, [f"{c}:{e}:iters" for c in SHAPES for e in (0, 100, 10, 1)])}}
+                   "run": (leg_payoff_run, [f"{c}:{e}:iters" for c in SHAPES for e in (0, 100, 10, 1)])},
+        "pair_map": {"call": (leg_pair_map_call, [f"{c}:{d}:{w}" for c in SHAPES for d in (32, "half") for w in ("cc", "all")]),
+                     "run": (leg_pair_map_run, [f"cfg3:{e}:iters" for e in (0, 100, 10)]),
+                     "host": (leg_pair_map_host, ["cfg3:32:roll", "cfg4:32:roll", "cfg5:32:roll", "cfg3:half:fft", "cfg4:half:fft",
+                                                  "cfg5:half:fft"])}}
 
 
 def main():
@@ -515,7 +604,7 @@ def main():
     if a.child:
         print("RESULT " + json.dumps(legs[a.child][0](a)), flush=True)
         return 0
-    width = 16 if a.record in ("clusters", "dwell", "policy", "payoff") else 6
+    width = 16 if a.record in ("clusters", "dwell", "policy", "payoff", "pair_map") else 6
     for leg in (a.legs.split(",") if a.legs else legs):
         for variant in legs[leg][1]:
             variant = variant.replace(":iters", f":{a.iters}")
