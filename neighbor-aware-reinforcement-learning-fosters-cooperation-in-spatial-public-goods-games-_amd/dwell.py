@@ -1,10 +1,10 @@
 """The per-agent strategy dwell record: persistence, two-time autocorrelation, strategy ages and
 cooperation frequency (spgg_dwell_*, spgg_abi.h).
 
-Unlike the records of records.KINDS this one is not a function of one instant: the device carries
+Unlike the other kinds of records.KINDS this one is not a function of one instant: the device carries
 three words per agent from one iteration to the next (BatchEngine.dwell_start), and `Dwell` is the
-in-run read-out of them on the schedule of every other record -- a records.Record that is not
-registered in KINDS.  With tracking started at t_ref (strategy = bit 0 of S, 0 = C):
+in-run read-out of them on the schedule of every other record; its two hooks start and stop the
+tracking.  With tracking started at t_ref (strategy = bit 0 of S, 0 = C):
 
     flips_i(t)  the number of j in t_ref .. t-1 with S_{j+1}[i] != S_j[i]
     since_i(t)  the smallest j >= t_ref with S_j[i] == .. == S_t[i];  age_i(t) = t - since_i(t)
@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib as C
-from .records import Record
+from .records import Record, _every, count, register, specs
 
 DWELL_AGE_BINS = C.DWELL_AGE_BINS   # age bin b = floor(log2(age + 1)), 0 .. 26 (age + 1 <= 2^26)
 DWELL_SLOTS = C.DWELL_SLOTS         # 7 counts and sums, then the 2 x DWELL_AGE_BINS age histogram
@@ -89,12 +89,57 @@ def host_dwell(planes, t_ref: int = 1):
     return dwell_row(prev, planes[0], flips, age, coop), np.stack([flips, age, coop])
 
 
+_FIELDS = ("flip_count", "strategy_age", "cooperation_frequency")      # BatchEngine.dwell_fields' keys, as DWELL_FIELD_DATASETS
+
+
+@register
 class Dwell(Record):
     """spgg_dwell_record of S_t: the DWELL_SLOTS int64 row; t0 is the reference iteration, at which
-    BatchEngine.run starts the tracking."""
+    BatchEngine.run starts the tracking; key (every,).
 
-    def __init__(self, every, t0, T):
+    run(dwell_every=k) also tracks the per-agent strategy dwell record (dwell_start at the run's first
+    iteration, the reference: one more launch after every step launch) and records its row (persistence,
+    autocorrelation, flips, cooperator time, strategy ages) on the schedule of the other records; read with
+    dwell_histories().  A run continued with the same k keeps its record and its reference, another k starts
+    afresh at the current t, 0 stops the tracking of an earlier run and drops its record; not on an engine that
+    steps in persistent launches.  The drop-in's dwell_fields: also the per-agent DWELL_FIELD_DATASETS of the
+    final state."""
+    name, getter = "dwell", "dwell_histories"
+    options = (("dwell_history_every", "dwell_every", 0, count), ("dwell_fields", None, False, bool))
+    files = specs(DWELL_DATASETS + DWELL_FIELD_DATASETS, optional=DWELL_FIELD_DATASETS, cooperation_frequency_final="float64")
+
+    def __init__(self, every, t0, T, key=None):
         super().__init__(every, t0, T, (int(every),))
+
+    @staticmethod
+    def validate(eng, dwell_every):
+        every = _every("dwell_every", dwell_every)
+        if every and eng.persistent:
+            raise ValueError("dwell_every: this engine steps in persistent launches, which have no launch "
+                             "boundary between two iterations for the dwell launch")
+        return (every,)
+
+    @classmethod
+    def starting(cls, eng):
+        """The tracking (re)starts with the new record.  dwell_start and dwell_stop drop the record, so one that
+        is still there has t0 == eng.dwell_t_ref: it is kept exactly if `every` matches."""
+        eng.dwell_start()
+
+    @classmethod
+    def unasked(cls, eng):
+        eng.dwell_stop()
+
+    @classmethod
+    def check_options(cls, values):
+        if values["dwell_fields"] and not values["dwell_history_every"]:
+            raise ValueError("dwell_fields needs dwell_history_every > 0 (nothing is tracked otherwise)")
+
+    @classmethod
+    def finals(cls, eng, k, extras):
+        if not extras["dwell_fields"]:
+            return {}
+        f = eng.dwell_fields(k)
+        return {name: f[key] for name, key in zip(DWELL_FIELD_DATASETS, _FIELDS)}
 
     def calls(self, eng):
         return [(eng.lib.spgg_dwell_record, (), DWELL_SLOTS, "int64")]

@@ -32,13 +32,13 @@ import torch
 
 from . import _lib as C
 from .algorithms import canonical_name
-from .dwell import DWELL_SLOTS, Dwell
-from . import pairmap
-from .payoff import PAYOFF_SLOTS, Payoff, pairs_width
-from .policy import Policy, policy_bin_edges, policy_width, split_row
 from .records import (KINDS, next_boundary, clusters_cap_text,  # noqa: F401  (the host models stay importable from here)
                       host_cluster_sizes, host_pair_counts, correlation_function, correlation_length,
                       reputation_bin_edges, host_reputation_pair_sums, reputation_correlation_function)
+from .dwell import DWELL_SLOTS          # (these four register their kinds after the three of records.py, in this order:
+from .policy import Policy, policy_bin_edges, policy_width, split_row      # the order of the datasets in the file)
+from .payoff import PAYOFF_SLOTS, Payoff, pairs_width
+from . import pairmap
 
 SNAPSHOT_ITERS = (1, 10, 100, 1000, 5000, 10000, 20000, 30000, 40000)  # spgg.py:153
 
@@ -332,7 +332,7 @@ class BatchEngine:
         self.snapshots = [dict() for _ in range(self.R)]
         self.png_frames = [dict() for _ in range(self.R)]
         self._flushed = False
-        self.records = {}          # name (records.KINDS, "dwell") -> the in-run Record of the last run that asked for it
+        self.records = {}          # name (records.KINDS) -> the in-run Record of the last run that asked for it
         self._final_cache = {}     # final-state observables (cluster_sizes, pair_counts, ...) until the next step
         self.dwell_t_ref = None    # the reference iteration of the strategy dwell record while it is tracked
         self._clusters_work = None   # the workspace of spgg_clusters_tiled, allocated on first use
@@ -486,12 +486,10 @@ class BatchEngine:
         C.check(self.lib.spgg_persistent(self.ctx, ctypes.byref(on), ctypes.byref(cap)), self.ctx, "spgg_persistent")
         self.persistent, self.persist_capacity = bool(on.value), int(cap.value)
         side = ctypes.c_int32()
-        for kind in KINDS:   # clusters_max_side, ...: the device path of the kind up to this lattice side
-            fn = getattr(self.lib, f"spgg_{kind}_max_side")
+        for x in (x for kind in KINDS.values() for x in kind.max_sides):   # clusters_max_side, ...: the device path up to this side
+            fn = getattr(self.lib, f"spgg_{x}_max_side")
             C.check(fn(self.ctx, ctypes.byref(side)), self.ctx, fn.__name__)
-            setattr(self, f"{kind}_max_side", int(side.value))
-        C.check(self.lib.spgg_payoff_pairs_max_side(self.ctx, ctypes.byref(side)), self.ctx, "spgg_payoff_pairs_max_side")
-        self.payoff_pairs_max_side = int(side.value)
+            setattr(self, f"{x}_max_side", int(side.value))
 
     def _draw_layout(self, ctx):
         """(ring slots, u32 words per replica and slot, key-snapshot slots) of the draw records."""
@@ -707,13 +705,7 @@ class BatchEngine:
         return self._loop
 
     def run(self, chunk: int = 256, snapshots: bool = True, png: bool = False,
-            progress: Optional[Callable[[int], None]] = None, clusters_every: int = 0,
-            clusters_periodic: bool = False, correlations_every: int = 0,
-            correlations_max_d: Optional[int] = None, reputation_every: int = 0,
-            reputation_bins: int = 20, reputation_max_d: Optional[int] = None, dwell_every: int = 0,
-            clusters_tiled=False, policy_every: int = 0, policy_bins: int = 32, policy_gap_range=2.0,
-            payoff_every: int = 0, payoff_max_d: Optional[int] = None, pair_map_every: int = 0,
-            pair_map_max_d: Optional[int] = None, pair_map_fields=(("coop", "coop"),)):
+            progress: Optional[Callable[[int], None]] = None, **record_options):
         """Execute iterations until `iterations` or every replica is absorbed.
 
         Turns of `chunk` iterations.  The absorbing-stop check of a turn is an asynchronous
@@ -724,87 +716,28 @@ class BatchEngine:
         replicas' launches change nothing, so results are unaffected; only the wall time of a
         run that absorbs early carries that turn.  Snapshot iterations sync.
 
-        In-run records (records.KINDS): *_every = k > 0 records the state at t = t0, t0+k, ... (t0 the
-        iteration the run starts at) on each replica group's own stream between the step launches of
-        t-1 and t -- a turn boundary there, no host sync; the stop-flag copies stay `chunk` iterations
-        apart -- one row per recorded iteration.  A run continued with the same settings keeps its
-        record, changed settings start a new one at the current t; every setting is checked
-        (ValueError) before anything is allocated or enqueued; with 0 nothing else is enqueued.
-          clusters_every: spgg_clusters of S_t (number of cooperator clusters, largest cluster, C-D
-            bonds; clusters_periodic: wrapped lattice); read with cluster_histories().  clusters_tiled:
-            False: the one-workgroup LDS kernel, lattices up to clusters_max_side; True: spgg_clusters_tiled
-            (one replica over many workgroups, any side) with the library's tile; an int: with that tile
-            side (8 .. 200).  Same record either way; part of the record's settings.
-          correlations_every: spgg_correlations of S_t, the cooperator pair counts at the distances
-            0 .. correlations_max_d (None: L // 2); read with correlation_histories().
-          reputation_every: spgg_reputation_hist of (S_t, R_t), the joint histogram strategy x bin
-            (reputation_bins bins over each replica's R_min .. R_max, the reference's edges); with
-            reputation_max_d also spgg_reputation_pairs, the pair sums of the int8 reputation plane at
-            the distances 0 .. reputation_max_d (not on an f64-reputation engine or above
-            reputation_max_side); read with reputation_histories().
-        dwell_every = k > 0 also tracks the per-agent strategy dwell record (dwell_start at the run's
-        first iteration, the reference: one more launch after every step launch) and records its row
-        (spgg_dwell_record: persistence, autocorrelation, flips, cooperator time, strategy ages) on the
-        same schedule; read with dwell_histories().  A run continued with the same k keeps its record
-        and its reference, another k starts afresh at the current t, 0 stops the tracking of an
-        earlier run and drops its record; not on an engine that steps in persistent launches.
-        policy_every = k > 0 records the learned policy field (spgg_policy, policy.py: the sixteen counts
-        class x strategy x state of the tables the agents act on at t -- the pending neighbour-influence
-        term rebuilt on the device --, the bonds between like and unlike classes and the histograms of
-        the two action gaps over policy_bins bins across policy_gap_range, a number g for (-g, g) or a
-        (lo, hi) pair, with a slot below and one above) on the same schedule; read with
-        policy_histories().  Settings as for the other records; not on an engine that steps in
-        persistent launches.
-        payoff_every = k > 0 records the payoff field (spgg_payoff_census, payoff.py: the census of the
-        agents by strategy, cooperating neighbours and group-cooperator total K -- the payoff
-        distribution for any parameters -- and the bonds between right / lower neighbours by their
-        difference in K; with payoff_max_d also spgg_payoff_pairs, the pair sums of K and c at the
-        distances 0 .. payoff_max_d) on the same schedule; read with payoff_histories().  Settings as
-        for the other records; a function of S_t alone, so allowed on an engine that steps in
-        persistent launches.
-        pair_map_every = k > 0 records 2-D pair maps of S_t (spgg_pair_map, pairmap.py: for every displacement
-        (dx, dy), dy = 0 .. D, dx = -D .. D, the cells with field a set whose partner has field b set) on
-        the same schedule, one map per (a, b) of pair_map_fields -- a tuple of distinct pairs of "coop"
-        (the cooperators) and "flip" (the agents that changed strategy in iteration t - 1); D =
-        pair_map_max_d, None: min(L // 2, 32).  A row holds (D + 1)(2 D + 1) int32 per replica and pair:
-        4 (D + 1)(2 D + 1) bytes, 8,580 at D = 32 and 81,204 at D = 100.  A distance whose call would exceed
-        the work cap (pairmap.work, pairmap.WORK_CAP) is refused; read with pair_map_histories().  Settings
-        as for the other records; a function of S_t alone, so allowed on an engine that steps in
-        persistent launches."""
-        policy_key = Policy.validate(self, policy_every, policy_bins, policy_gap_range)   # (before any allocation)
-        payoff_key = Payoff.validate(self, payoff_every, payoff_max_d)
-        pair_map_key = pairmap.PairMap.validate(self, pair_map_every, pair_map_max_d, pair_map_fields)
-        asked = {"clusters": (clusters_every, clusters_periodic, clusters_tiled), "correlations": (correlations_every, correlations_max_d),
-                 "reputation": (reputation_every, reputation_bins, reputation_max_d)}
-        keys = {name: KINDS[name].validate(self, *a) for name, a in asked.items()}   # (before any allocation)
-        dwell_every = int(dwell_every)
-        if dwell_every < 0:
-            raise ValueError("dwell_every must be >= 0")
-        if dwell_every and self.persistent:
-            raise ValueError("dwell_every: this engine steps in persistent launches, which have no launch "
-                             "boundary between two iterations for the dwell launch")
-        active = [self._record(name, key) for name, key in keys.items() if key[0]]
-        if dwell_every:
-            rec = self.records.get("dwell")
-            if rec is None or rec.every != dwell_every or self.dwell_t_ref != rec.t0:
-                self.dwell_start()
-                rec = self.records["dwell"] = Dwell(dwell_every, self.t, self.T)
-                rec.plan = rec.calls(self)
-                rec.out = [torch.zeros((self.R, rec.rows, DWELL_SLOTS), dtype=torch.int64, device=self.dev)]
-            active.append(rec)
-        elif "dwell" in self.records:
-            self.dwell_stop()
-        if policy_key[0]:
-            rec = self.records.get("policy")
-            if rec is None or rec.key != policy_key:
-                rec = self.records["policy"] = Policy(policy_key[0], self.t, self.T, policy_key)
-                rec.plan = rec.calls(self)
-                rec.out = [torch.zeros((self.R, rec.rows, policy_width(policy_key[1])), dtype=torch.int32, device=self.dev)]
-            active.append(rec)
-        if payoff_key[0]:
-            active.append(self._record("payoff", payoff_key, Payoff))
-        if pair_map_key[0]:
-            active.append(self._record("pair_map", pair_map_key, pairmap.PairMap))
+        In-run records (record_options: the BatchEngine.run keywords of the kinds of records.KINDS --
+        clusters_every, clusters_periodic, clusters_tiled, correlations_every, correlations_max_d,
+        reputation_every, reputation_bins, reputation_max_d, dwell_every, policy_every, policy_bins,
+        policy_gap_range, payoff_every, payoff_max_d, pair_map_every, pair_map_max_d, pair_map_fields --
+        at the defaults of the kinds' `options`; each kind's docstring says what its keywords record):
+        *_every = k > 0 records the state at t = t0, t0+k, ... (t0 the iteration the run starts at) on each
+        replica group's own stream between the step launches of t-1 and t -- a turn boundary there, no host
+        sync; the stop-flag copies stay `chunk` iterations apart -- one row per recorded iteration.  A run
+        continued with the same settings keeps its record, changed settings start a new one at the current
+        t; every setting of every kind is checked (ValueError) before anything is allocated or enqueued; with
+        0 nothing else is enqueued, and an earlier run's record stays readable (dwell's is dropped)."""
+        asked = {name: {kw: record_options.pop(kw, default) for _attr, kw, default, _conv in kind.options if kw}
+                 for name, kind in KINDS.items()}
+        if record_options:
+            raise TypeError(f"run() got an unexpected keyword argument {next(iter(record_options))!r}")
+        keys = {name: KINDS[name].validate(self, **kw) for name, kw in asked.items()}   # (all, before any allocation)
+        active = []
+        for name, key in keys.items():
+            if key[0]:
+                active.append(self._record(name, key))
+            elif name in self.records:
+                KINDS[name].unasked(self)
         stops = set()
         if snapshots:
             stops |= {i for i in SNAPSHOT_ITERS if i <= self.T}
@@ -924,21 +857,31 @@ class BatchEngine:
                     g["ctx"], fn.__name__)
         self._enqueue(one)
 
-    def _record(self, name, key, kind=None):
-        """The in-run Record `name` (of records.KINDS, or of the given class) with the validated settings
-        `key`: the one a run with the same settings left, or a new one that starts at the current iteration."""
+    def _record(self, name, key):
+        """The in-run Record of the kind `name` with the validated settings `key`: the one a run with the
+        same settings left, or a new one that starts at the current iteration."""
         rec = self.records.get(name)
         if rec is None or rec.key != key:
-            rec = self.records[name] = (kind or KINDS[name])(key[0], self.t, self.T, key)
+            KINDS[name].starting(self)
+            rec = self.records[name] = KINDS[name](key[0], self.t, self.T, key)
             rec.plan = rec.calls(self)
             rec.out = [torch.zeros((self.R, rec.rows, w), dtype=getattr(torch, dt), device=self.dev)
                        for _fn, _args, w, dt in rec.plan]
         return rec
 
-    def _histories(self, name, what):
+    def _histories(self, name):
         if name not in self.records:
-            raise ValueError(f"{what} with k > 0 first")
+            raise ValueError(f"{KINDS[name].getter}: run({KINDS[name].options[0][1]}=k) with k > 0 first")
         return self.records[name].histories(self)
+
+    def _work(self, attr, width, dtype=torch.int32):
+        """The (R, width) device workspace held as self.<attr>: allocated on first use, a new one if asked
+        for more (a record keeps the one it was planned with); _observe hands each replica group its slice."""
+        ws = getattr(self, attr)
+        if ws is None or ws.shape[1] < int(width):
+            ws = torch.empty((self.R, int(width)), dtype=dtype, device=self.dev)
+            setattr(self, attr, ws)
+        return ws
 
     def _final(self, key, fn, args, width, dtype=torch.int32):
         """The (R, width) host array of one observable call on the final state, all replicas at
@@ -975,19 +918,16 @@ class BatchEngine:
     def _clusters_workspace(self):
         """The (R, words) int32 workspace of spgg_clusters_tiled (parent and count planes, 8 B per agent, plus the
         flag words), allocated on first use; _observe hands each replica group its replica slice."""
-        if self._clusters_work is None:
-            words = ctypes.c_int64(0)
-            C.check(self.lib.spgg_clusters_tiled_workspace(self.ctx, ctypes.byref(words)), self.ctx,
-                    "spgg_clusters_tiled_workspace")
-            self._clusters_work = torch.empty((self.R, int(words.value)), dtype=torch.int32, device=self.dev)
-        return self._clusters_work
+        words = ctypes.c_int64(0)
+        C.check(self.lib.spgg_clusters_tiled_workspace(self.ctx, ctypes.byref(words)), self.ctx, "spgg_clusters_tiled_workspace")
+        return self._work("_clusters_work", words.value)
 
     def cluster_histories(self):
         """Per replica, the in-run cluster record of run(clusters_every=k): cluster_history_iters
         (the recorded iterations t <= last_iteration, so a replica absorbed at s keeps the record
         of S_s if s was recorded), cluster_count_history, largest_cluster_history and
         cd_bond_history (C-D bonds of the wrapped lattice), all int64."""
-        return self._histories("clusters", "cluster_histories: run(clusters_every=k)")
+        return self._histories("clusters")
 
     def pair_counts(self, k, max_d: Optional[int] = None) -> np.ndarray:
         """int64 (2, D+1) cooperator pair counts of replica k in the state final_state(k) returns,
@@ -1007,7 +947,7 @@ class BatchEngine:
         """Per replica, the in-run pair-count record of run(correlations_every=k):
         correlation_history_iters (as cluster_history_iters), pair_count_rows_history and
         pair_count_cols_history, int64 (m, D+1)."""
-        return self._histories("correlations", "correlation_histories: run(correlations_every=k)")
+        return self._histories("correlations")
 
     def _reputation_edges(self, bins, edges=None):
         """Device f64 (R, bins + 1) edges: each replica's reference edges over its R_min .. R_max,
@@ -1064,7 +1004,7 @@ class BatchEngine:
         reputation_hist_history int64 (m, 2, bins) and reputation_bin_edges f64 (bins + 1,); with
         reputation_max_d also reputation_sum_history (m,), reputation_pair_rows_history and
         reputation_pair_cols_history (m, D+1), int64 in units of reputation_unit (squared)."""
-        return self._histories("reputation", "reputation_histories: run(reputation_every=k)")
+        return self._histories("reputation")
 
     # -- the strategy dwell record (dwell.py; spgg_dwell_*) -------------------
     def dwell_start(self):
@@ -1128,7 +1068,7 @@ class BatchEngine:
         autocorrelation_history (m, 3: same as the reference, cooperator then and now, cooperators),
         flip_total_history, cooperator_time_history (m,) and strategy_age_hist_history
         (m, 2, DWELL_AGE_BINS), all int64."""
-        return self._histories("dwell", "dwell_histories: run(dwell_every=k)")
+        return self._histories("dwell")
 
     # -- the learned policy record (policy.py; spgg_policy) --------------------
     def _spgg_policy(self, ctx, t, *rest):
@@ -1143,9 +1083,7 @@ class BatchEngine:
 
     def _policy_plane(self):
         """The (R, n) uint8 plane spgg_policy writes (class | strategy << 2 | state << 3), allocated once."""
-        if self._policy_work is None:
-            self._policy_work = torch.empty((self.R, self.n), dtype=torch.uint8, device=self.dev)
-        return self._policy_work
+        return self._work("_policy_work", self.n, torch.uint8)
 
     def _policy_edges(self, bins, gap_range):
         """Device f64 (R, bins + 1): the gap histogram's edges, the same for every replica."""
@@ -1183,14 +1121,12 @@ class BatchEngine:
         policy_history_iters (the recorded iterations t <= last_iteration), policy_count_history int64
         (m, 4, 2, 2), policy_bond_history (m, 5), policy_gap_hist_history (m, 2, 2, bins + 2) and
         policy_gap_bin_edges f64 (bins + 1,)."""
-        return self._histories("policy", "policy_histories: run(policy_every=k)")
+        return self._histories("policy")
 
     # -- the payoff record (payoff.py; spgg_payoff_census, spgg_payoff_pairs) --------------------
     def _payoff_plane(self):
         """The (R, n) uint8 plane spgg_payoff_census writes (K | strategy << 5 | m << 6), allocated once."""
-        if self._payoff_work is None:
-            self._payoff_work = torch.empty((self.R, self.n), dtype=torch.uint8, device=self.dev)
-        return self._payoff_work
+        return self._work("_payoff_work", self.n, torch.uint8)
 
     def _payoff_final(self):
         if "payoff_census" not in self._final_cache:
@@ -1227,7 +1163,7 @@ class BatchEngine:
         payoff_history_iters (the recorded iterations t <= last_iteration), payoff_census_history int64
         (m, 2, 5, 26), payoff_bond_history (m, 103: bond_cd, bond_cc, bond_dd) and payoff_values f64
         (2, 26); with payoff_max_d also payoff_pair_sums_history (m, 2 + 6 (D + 1))."""
-        return self._histories("payoff", "payoff_histories: run(payoff_every=k)")
+        return self._histories("payoff")
 
     # -- the pair maps (pairmap.py; spgg_pair_map) ---------------------------------------------
     def _pair_map_work(self, D):
@@ -1236,9 +1172,7 @@ class BatchEngine:
         record keeps the one it was planned with)."""
         words = ctypes.c_int64(0)
         C.check(self.lib.spgg_pair_map_workspace(self.ctx, int(D), ctypes.byref(words)), self.ctx, "spgg_pair_map_workspace")
-        if self._pair_map_ws is None or self._pair_map_ws.shape[1] < int(words.value):
-            self._pair_map_ws = torch.empty((self.R, int(words.value)), dtype=torch.int32, device=self.dev)
-        return self._pair_map_ws
+        return self._work("_pair_map_ws", words.value)
 
     def pair_map(self, k, a: str = "coop", b: str = "coop", max_d: Optional[int] = None) -> np.ndarray:
         """int64 (D + 1, 2 D + 1) pair map of replica k in the state the engine is in (after run():
@@ -1259,7 +1193,7 @@ class BatchEngine:
         """Per replica, the in-run pair-map record of run(pair_map_every=k): pair_map_history_iters (the
         recorded iterations t <= last_iteration), one pair_map_<a>_<b>_history int64 (m, D + 1, 2 D + 1) per
         field pair, and pair_map_max_distance (D)."""
-        return self._histories("pair_map", "pair_map_histories: run(pair_map_every=k)")
+        return self._histories("pair_map")
 
     def finalize_history(self):
         """Derived history slots (payoff sums, w_P*P, w_rep*rr, reward over D) of every

@@ -12,15 +12,14 @@ displacements (`full_plane`), the direction-averaged G(r) (`radial_function`) an
 structure factor S(k) (`structure_factor`).
 
 `host_fields` / `host_pair_map` are the NumPy models (np.roll, the definition itself; nothing of the
-device's scheme); `PairMap` the in-run record (a records.Record that is not registered in
-records.KINDS, as payoff.Payoff is not).
+device's scheme); `PairMap` the in-run record (the kind "pair_map" of records.KINDS).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib as C
-from .records import Record, _every
+from .records import Record, _every, asis, count, register, specs
 
 FIELDS = {"coop": C.FIELD_COOP, "flip": C.FIELD_FLIP}
 WORK_CAP = C.PAIR_MAP_WORK_CAP
@@ -148,13 +147,26 @@ def field_pairs(fields):
     return pairs
 
 
+@register
 class PairMap(Record):
     """spgg_pair_map of S_t, one call and one int32 tensor of (D + 1)(2 D + 1) values per field pair; key
-    (every, D, fields)."""
+    (every, D, fields).
+
+    run(pair_map_every=k) records 2-D pair maps of S_t (for every displacement (dx, dy), dy = 0 .. D,
+    dx = -D .. D, the cells with field a set whose partner has field b set) on the schedule of the other
+    records, one map per (a, b) of pair_map_fields -- a tuple of distinct pairs of "coop" (the cooperators)
+    and "flip" (the agents that changed strategy in iteration t - 1); D = pair_map_max_d, None:
+    min(L // 2, 32).  A row holds (D + 1)(2 D + 1) int32 per replica and pair: 4 (D + 1)(2 D + 1) bytes, 8,580
+    at D = 32 and 81,204 at D = 100.  A distance whose call would exceed the work cap (work, WORK_CAP) is
+    refused; read with pair_map_histories().  Settings as for the other records; a function of S_t alone, so
+    allowed on an engine that steps in persistent launches."""
+    name, getter = "pair_map", "pair_map_histories"
+    options = (("pair_map_history_every", "pair_map_every", 0, count), ("pair_map_max_distance", "pair_map_max_d", None, asis),
+               ("pair_map_fields", "pair_map_fields", (("coop", "coop"),), lambda v: tuple(tuple(p) for p in v)))
 
     @staticmethod
-    def validate(eng, every, max_d, fields, what="pair_map_every"):
-        every = _every(what, every)
+    def validate(eng, pair_map_every, pair_map_max_d, pair_map_fields, what="pair_map_every"):
+        every, max_d, fields = _every(what, pair_map_every), pair_map_max_d, pair_map_fields
         if not every:
             return 0, None, ()
         D = min(eng.L // 2, IN_RUN_MAX_D) if max_d is None else int(max_d)
@@ -166,6 +178,18 @@ class PairMap(Record):
             raise ValueError(f"pair_map_max_d = {D}: one call would be {w} word blocks, above the cap {WORK_CAP} "
                              "(pairmap.work; a smaller distance, or map snapshots on the host: pairmap.host_pair_map)")
         return every, D, pairs
+
+    @classmethod
+    def check_options(cls, values):
+        if values["pair_map_max_distance"] is not None and not values["pair_map_history_every"]:
+            raise ValueError("pair_map_max_distance needs pair_map_history_every > 0 (nothing is recorded otherwise)")
+        values["pair_map_fields"] = field_pairs(values["pair_map_fields"])
+
+    @classmethod
+    def file_datasets(cls, hist):
+        """The iterations, one map per field pair (the key's pairs: the names datasets gave them), the distance."""
+        maps = [name for name in hist if name not in (PAIR_MAP_ITERS_DATASET, PAIR_MAP_DISTANCE_DATASET)]
+        return specs([PAIR_MAP_ITERS_DATASET, *maps, PAIR_MAP_DISTANCE_DATASET])
 
     def calls(self, eng):
         _, D, pairs = self.key

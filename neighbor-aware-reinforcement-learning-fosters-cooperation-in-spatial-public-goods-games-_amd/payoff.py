@@ -15,15 +15,14 @@ in K: bond_cd[K_C - K_D + 25], bond_cc[|dK|], bond_dd[|dK|].  The pair sums of K
 0 .. D along rows and columns give the two-point function of the payoff.
 
 `host_payoff_census` / `host_payoff_pairs` are the NumPy models (np.roll, nothing of the device's
-scheme); `Payoff` the in-run record (a records.Record that is not registered in records.KINDS, as
-dwell.Dwell and policy.Policy are not).
+scheme); `Payoff` the in-run record (the kind "payoff" of records.KINDS).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib as C
-from .records import Record, _every
+from .records import Record, _every, asis, count, register, specs
 
 PAYOFF_SLOTS = C.PAYOFF_SLOTS
 MAX_K = 25
@@ -190,13 +189,27 @@ def payoff_correlation_function(pairs, n, params, max_d=None):
     return (second - mean[..., None] ** 2) / (den * den)
 
 
+@register
 class Payoff(Record):
     """spgg_payoff_census of S_t: the PAYOFF_SLOTS int32 row; with D not None also spgg_payoff_pairs of
-    the plane the census wrote: pairs_width(D) int64; key (every, D)."""
+    the plane the census wrote: pairs_width(D) int64; key (every, D).
+
+    run(payoff_every=k) records the payoff field (the census of the agents by strategy, cooperating neighbours
+    and group-cooperator total K -- the payoff distribution for any parameters -- and the bonds between right /
+    lower neighbours by their difference in K; with payoff_max_d also the pair sums of K and c at the distances
+    0 .. payoff_max_d) on the schedule of the other records; read with payoff_histories().  Settings as for the
+    other records; a function of S_t alone, so allowed on an engine that steps in persistent launches.  The
+    drop-in's payoff_map_final: also the final state's per-agent map K | strategy << 5 | (m & 3) << 6 (uint8)
+    as PAYOFF_MAP_DATASET."""
+    name, getter, max_sides = "payoff", "payoff_histories", ("payoff_pairs",)
+    options = (("payoff_history_every", "payoff_every", 0, count), ("payoff_max_distance", "payoff_max_d", None, asis),
+               ("payoff_map_final", None, False, bool))
+    files = specs(PAYOFF_DATASETS + (PAYOFF_PAIRS_DATASET, PAYOFF_MAP_DATASET), optional=(PAYOFF_PAIRS_DATASET, PAYOFF_MAP_DATASET),
+                  payoff_values="float64", payoff_map_final="uint8")
 
     @staticmethod
-    def validate(eng, every, max_d, what="payoff_every"):
-        every = _every(what, every)
+    def validate(eng, payoff_every, payoff_max_d, what="payoff_every"):
+        every, max_d = _every(what, payoff_every), payoff_max_d
         D = None if max_d is None else int(max_d)
         if D is not None and not every:
             raise ValueError("payoff_max_d needs payoff_every > 0 (nothing is recorded otherwise)")
@@ -207,6 +220,16 @@ class Payoff(Record):
             if not 0 <= D <= eng.L // 2:
                 raise ValueError(f"payoff_max_d must lie in 0 .. L // 2 = {eng.L // 2}, got {D}")
         return every, D
+
+    @classmethod
+    def check_options(cls, values):
+        if (values["payoff_map_final"] or values["payoff_max_distance"] is not None) and not values["payoff_history_every"]:
+            raise ValueError("payoff_max_distance and payoff_map_final need payoff_history_every > 0 (nothing is "
+                             "recorded otherwise)")
+
+    @classmethod
+    def finals(cls, eng, k, extras):
+        return {PAYOFF_MAP_DATASET: eng.payoff_map(k)} if extras["payoff_map_final"] else {}
 
     def calls(self, eng):
         D, plane = self.key[1], eng._payoff_plane()

@@ -16,15 +16,14 @@ below the first edge, slots 1 .. bins np.histogram's, slot bins + 1 the gaps abo
 
 Between two step launches the device's Q buffer is not T: it lacks the last iteration's
 neighbour-influence term, which spgg_policy rebuilds on the device.  `host_policy_record` is the
-NumPy model of the record given T itself; `Policy` the in-run record (a records.Record that is not
-registered in records.KINDS, as dwell.Dwell is not).
+NumPy model of the record given T itself; `Policy` the in-run record (the kind "policy" of records.KINDS).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib as C
-from .records import Record, _every
+from .records import Record, _every, asis, count, register, specs
 
 POLICY_COUNTS = C.POLICY_COUNTS     # 16 counts + 4 bonds_same + bonds_mixed
 POLICY_MAX_BINS = 256
@@ -108,12 +107,26 @@ def split_row(row, bins):
             row[..., POLICY_COUNTS:].reshape(lead + (2, 2, int(bins) + 2)))
 
 
+@register
 class Policy(Record):
-    """spgg_policy of iteration t: the policy_width(bins) int32 row; key (every, bins, (lo, hi))."""
+    """spgg_policy of iteration t: the policy_width(bins) int32 row; key (every, bins, (lo, hi)).
+
+    run(policy_every=k) records the learned policy field (the sixteen counts class x strategy x state of the
+    tables the agents act on at t -- the pending neighbour-influence term rebuilt on the device --, the bonds
+    between like and unlike classes and the histograms of the two action gaps over policy_bins bins across
+    policy_gap_range, a number g for (-g, g) or a (lo, hi) pair, with a slot below and one above) on the
+    schedule of the other records; read with policy_histories().  Settings as for the other records; not on
+    an engine that steps in persistent launches.  The drop-in's policy_map_final: also the final state's
+    per-agent map class | strategy << 2 | state << 3 (uint8) as POLICY_MAP_DATASET."""
+    name, getter = "policy", "policy_histories"
+    options = (("policy_history_every", "policy_every", 0, count), ("policy_history_bins", "policy_bins", 32, int),
+               ("policy_history_gap_range", "policy_gap_range", 2.0, asis), ("policy_map_final", None, False, bool))
+    files = specs(POLICY_DATASETS + (POLICY_MAP_DATASET,), optional=(POLICY_MAP_DATASET,), policy_gap_bin_edges="float64",
+                  policy_map_final="uint8")
 
     @staticmethod
-    def validate(eng, every, bins, gap_range, what="policy_every"):
-        every, bins = _every(what, every), int(bins)
+    def validate(eng, policy_every, policy_bins, policy_gap_range, what="policy_every"):
+        every, bins, gap_range = _every(what, policy_every), int(policy_bins), policy_gap_range
         if not every:
             return 0, bins, None
         if eng.persistent:
@@ -122,6 +135,15 @@ class Policy(Record):
         if not 1 <= bins <= POLICY_MAX_BINS:
             raise ValueError(f"policy_bins must lie in 1 .. {POLICY_MAX_BINS}, got {bins}")
         return every, bins, _range(gap_range)
+
+    @classmethod
+    def check_options(cls, values):
+        if values["policy_map_final"] and not values["policy_history_every"]:
+            raise ValueError("policy_map_final needs policy_history_every > 0 (nothing is recorded otherwise)")
+
+    @classmethod
+    def finals(cls, eng, k, extras):
+        return {POLICY_MAP_DATASET: eng.policy_map(k)} if extras["policy_map_final"] else {}
 
     def calls(self, eng):
         _, bins, rng = self.key

@@ -1,14 +1,24 @@
 """The in-run device records of BatchEngine.run and the host-side models of what they hold.
 
 A `Record` is one stream of observations of the running lattice: every `every` iterations from `t0`
-on, one ABI call per device tensor writes one row.  The kinds (KINDS) differ only in their settings,
-calls and datasets.  The schedule is plain Python; the engine allocates and enqueues (_observe).
+on, one ABI call per device tensor writes one row.  The kinds (KINDS, the registry of all of them) differ
+only in their class data -- options and datasets -- and in their settings, calls and rows.  The schedule
+is plain Python; the engine allocates and enqueues (_observe).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib as C
+
+KINDS = {}      # name -> kind, in the order the kinds' datasets have in the file (register)
+
+
+def register(kind):
+    """Class decorator: enter a kind into KINDS.  clusters, correlations and reputation register here, dwell,
+    policy, payoff and pair_map in their own modules, which engine.py imports in that order."""
+    KINDS[kind.name] = kind
+    return kind
 
 
 def next_boundary(t, stops, check_at, end, records=()):
@@ -25,10 +35,33 @@ def _every(name, value) -> int:
     return value
 
 
+def count(v) -> int:
+    """An *_every option of the drop-in: None and 0 switch the record off."""
+    return int(v or 0)
+
+
+def asis(v):
+    return v
+
+
+def specs(names, optional=(), **dtypes):
+    """A kind's `files` from dataset names in file order: int64 unless `dtypes` says float64 or uint8."""
+    return tuple((name, dtypes.get(name, "int64"), name in optional) for name in names)
+
+
 class Record:
     """A record of the iterations t0, t0 + every, ... <= T: `key` its settings (every first), `out`
     its device tensors, each (R, rows, width) with one row per recorded iteration, `plan` the (ABI
-    function, its scalar arguments, width, dtype) of the call that fills each (a kind's calls)."""
+    function, its scalar arguments, width, dtype) of the call that fills each (a kind's calls).
+
+    A kind states as class data what its callers need: `name` (its key in KINDS and BatchEngine.records),
+    `getter` (BatchEngine's *_histories method), `options` -- one (drop-in attribute, BatchEngine.run keyword
+    or None for an option of the drop-in alone, default, conversion) each, the *_every option first --, `files`
+    -- one (dataset, dtype, optional) each, in file order -- and `max_sides`, the x of the spgg_<x>_max_side
+    entry points its validate reads as eng.<x>_max_side.  validate(eng, **its run keywords) -> key raises the
+    ValueErrors of run(); calls(eng) is the plan; datasets(eng, k, its, *rows) one replica's history."""
+    name = getter = None
+    options = files = max_sides = ()
 
     def __init__(self, every, t0, T, key=()):
         self.every, self.t0, self.key = int(every), int(t0), key
@@ -61,6 +94,31 @@ class Record:
         its = [self.iters(eng.last_iteration(k)) for k in range(eng.R)]
         return [self.datasets(eng, k, its[k], *[h[k, :len(its[k])] for h in host]) for k in range(eng.R)]
 
+    # -- what a kind may add (dwell.Dwell has the first two; no kind needs all) --
+    @classmethod
+    def starting(cls, eng):
+        """BatchEngine.run is about to create a new record of the kind."""
+
+    @classmethod
+    def unasked(cls, eng):
+        """BatchEngine.run was asked for the kind with every == 0 while an earlier run's record exists (which
+        stays readable unless the kind drops it here)."""
+
+    @classmethod
+    def check_options(cls, values):
+        """The drop-in's cross-checks (ValueError) of the kind's converted option values, attribute -> value;
+        may normalise them in place."""
+
+    @classmethod
+    def finals(cls, eng, k, extras) -> dict:
+        """The final-state datasets of replica k that the drop-in-only options `extras` ask for."""
+        return {}
+
+    @classmethod
+    def file_datasets(cls, hist):
+        """`files` of one replica's history."""
+        return cls.files
+
 
 def clusters_tile(tiled):
     """The tile side a clusters_tiled value asks for: False -> None (the one-workgroup LDS kernel),
@@ -84,14 +142,39 @@ def clusters_cap_text(tiled) -> str:
             f"a seam union's retry cap {C.CLUSTERS_TILED_MAX_RETRIES})")
 
 
+def _tiled(v):
+    return v if isinstance(v, bool) else (int(v) if v else False)
+
+
+CLUSTER_DATASETS = ("cluster_history_iters", "cluster_count_history", "largest_cluster_history", "cd_bond_history")
+CORRELATION_DATASETS = ("correlation_history_iters", "pair_count_rows_history", "pair_count_cols_history")
+# the last four only with reputation_max_distance set (BatchEngine.reputation_histories)
+REPUTATION_DATASETS = ("reputation_history_iters", "reputation_hist_history", "reputation_bin_edges",
+                       "reputation_sum_history", "reputation_pair_rows_history", "reputation_pair_cols_history",
+                       "reputation_unit")
+
+
+@register
 class Clusters(Record):
     """spgg_clusters of S_t: (clusters, largest cluster, C-D bonds) int32; key (every, periodic, tile): tile
-    None for the one-workgroup LDS kernel, else the tile side of spgg_clusters_tiled (0: the library's)."""
+    None for the one-workgroup LDS kernel, else the tile side of spgg_clusters_tiled (0: the library's).
+
+    run(clusters_every=k): the number of cooperator clusters, the largest cluster and the C-D bonds;
+    clusters_periodic: of the wrapped lattice (the drop-in's final cluster_sizes dataset never wraps:
+    spgg.py:631); read with cluster_histories().  clusters_tiled: False: the one-workgroup LDS kernel, lattices
+    up to clusters_max_side; True: spgg_clusters_tiled (one replica over many workgroups, any side) with the
+    library's tile; an int: with that tile side (8 .. 200).  Same record either way; part of the record's
+    settings; needs clusters_every > 0."""
+    name, getter, max_sides = "clusters", "cluster_histories", ("clusters",)
+    options = (("cluster_history_every", "clusters_every", 0, count),
+               ("cluster_history_periodic", "clusters_periodic", False, bool),
+               ("cluster_history_tiled", "clusters_tiled", False, _tiled))
+    files = specs(CLUSTER_DATASETS)
 
     @staticmethod
-    def validate(eng, every, periodic, tiled=False):
-        every = _every("clusters_every", every)
-        tile = clusters_tile(tiled)
+    def validate(eng, clusters_every, clusters_periodic, clusters_tiled=False):
+        every, periodic = _every("clusters_every", clusters_every), clusters_periodic
+        tile = clusters_tile(clusters_tiled)
         if tile is not None and not every:
             raise ValueError("clusters_tiled needs clusters_every > 0 (nothing is recorded otherwise)")
         if every and tile is None and eng.L > eng.clusters_max_side:
@@ -115,12 +198,20 @@ class Clusters(Record):
                     largest_cluster_history=r[:, 1].copy(), cd_bond_history=r[:, 2].copy())
 
 
+@register
 class Correlations(Record):
-    """spgg_correlations of S_t: D + 1 row then D + 1 column pair counts, int32; key (every, D)."""
+    """spgg_correlations of S_t: D + 1 row then D + 1 column pair counts, int32; key (every, D).
+
+    run(correlations_every=k): the cooperator pair counts along rows and columns at the distances
+    0 .. correlations_max_d (None: L // 2); read with correlation_histories()."""
+    name, getter, max_sides = "correlations", "correlation_histories", ("correlations",)
+    options = (("correlation_history_every", "correlations_every", 0, count),
+               ("correlation_max_distance", "correlations_max_d", None, asis))
+    files = specs(CORRELATION_DATASETS)
 
     @staticmethod
-    def validate(eng, every, max_d):
-        every = _every("correlations_every", every)
+    def validate(eng, correlations_every, correlations_max_d):
+        every, max_d = _every("correlations_every", correlations_every), correlations_max_d
         D = eng.L // 2 if max_d is None else int(max_d)
         if every and not 0 <= D <= eng.L // 2:
             raise ValueError(f"correlations_max_d must lie in 0 .. L // 2 = {eng.L // 2}, got {D}")
@@ -138,14 +229,26 @@ class Correlations(Record):
                     pair_count_cols_history=r[:, D + 1:].copy())
 
 
+@register
 class Reputation(Record):
     """spgg_reputation_hist of (S_t, R_t): 2 x bins counts, int32, over each replica's reference edges; with
     D not None also spgg_reputation_pairs of the int8 plane: sum, D + 1 row and D + 1 column sums,
-    int64; key (every, bins, D)."""
+    int64; key (every, bins, D).
+
+    run(reputation_every=k): the joint histogram strategy x bin (reputation_bins bins over each replica's
+    R_min .. R_max, the reference's edges); with reputation_max_d also the pair sums of the int8 reputation
+    plane at the distances 0 .. reputation_max_d (not on an f64-reputation engine or above
+    reputation_max_side); read with reputation_histories()."""
+    name, getter, max_sides = "reputation", "reputation_histories", ("reputation",)
+    options = (("reputation_history_every", "reputation_every", 0, count),
+               ("reputation_history_bins", "reputation_bins", 20, int),
+               ("reputation_max_distance", "reputation_max_d", None, asis))
+    files = specs(REPUTATION_DATASETS, optional=REPUTATION_DATASETS[3:], reputation_bin_edges="float64",
+                  reputation_unit="float64")
 
     @staticmethod
-    def validate(eng, every, bins, max_d):
-        every, bins = _every("reputation_every", every), int(bins)
+    def validate(eng, reputation_every, reputation_bins, reputation_max_d):
+        every, bins, max_d = _every("reputation_every", reputation_every), int(reputation_bins), reputation_max_d
         D = None if max_d is None else int(max_d)
         if every and not 1 <= bins <= 256:
             raise ValueError(f"reputation_bins must lie in 1 .. 256, got {bins}")
@@ -174,9 +277,6 @@ class Reputation(Record):
             d.update(reputation_sum_history=r[:, 0].copy(), reputation_pair_rows_history=r[:, 1:D + 2].copy(),
                      reputation_pair_cols_history=r[:, D + 2:].copy(), reputation_unit=np.float64(eng.rep_units[k]))
         return d
-
-
-KINDS = {"clusters": Clusters, "correlations": Correlations, "reputation": Reputation}
 
 
 def host_cluster_sizes(S, periodic: bool = False) -> np.ndarray:

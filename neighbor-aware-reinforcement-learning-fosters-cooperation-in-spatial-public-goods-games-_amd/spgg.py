@@ -15,12 +15,9 @@ import os
 import numpy as np
 
 from . import algorithms as A
-from .dwell import DWELL_DATASETS, DWELL_FIELD_DATASETS
 from .engine import BatchEngine, InitState, ReplicaParams, SNAPSHOT_ITERS
 from .h5io import open_writer
-from .pairmap import PAIR_MAP_DISTANCE_DATASET, PAIR_MAP_ITERS_DATASET, field_pairs
-from .payoff import PAYOFF_DATASETS, PAYOFF_MAP_DATASET, PAYOFF_PAIRS_DATASET
-from .policy import POLICY_DATASETS, POLICY_MAP_DATASET
+from .records import KINDS, CLUSTER_DATASETS, CORRELATION_DATASETS, REPUTATION_DATASETS  # noqa: F401  (read from here)
 
 
 def _sum5(A_):
@@ -32,193 +29,42 @@ def sum_position_and_neighbors(A_):
     return _sum5(A_)
 
 
-def _count(v):
-    return int(v or 0)
+# The in-run record options: class attributes of SPGG (not constructor arguments; the sweep takes them among
+# its model overrides), name -> (default, BatchEngine.run keyword argument or None for an option of the drop-in
+# alone, conversion), from the kinds of records.KINDS, whose docstrings say what each records.  *_every = k > 0:
+# also record the state at t = 1, 1+k, ... on the device and write the record as more datasets after the
+# reference's own, the kinds in the registry's order; 0: the reference's file.
+RECORD_OPTIONS = {attr: (default, kw, conv) for kind in KINDS.values() for attr, kw, default, conv in kind.options}
 
 
-# The in-run record options: class attributes of SPGG (not constructor arguments; the sweep takes
-# them among its model overrides), name -> (default, BatchEngine.run keyword argument, conversion).
-# *_every = k > 0: also record S_t (and R_t) at t = 1, 1+k, ... on the device and write the record as
-# more datasets after the reference's own; 0: the reference's file.
-RECORD_OPTIONS = {
-    # the cooperator clusters (count, largest, C-D bonds: CLUSTER_DATASETS); _periodic: they wrap
-    # with the lattice (the final cluster_sizes dataset never does: spgg.py:631)
-    "cluster_history_every": (0, "clusters_every", _count),
-    "cluster_history_periodic": (False, "clusters_periodic", bool),
-    # the cooperator pair counts along rows and columns at the distances 0 .. correlation_max_distance
-    # (None: L // 2; CORRELATION_DATASETS)
-    "correlation_history_every": (0, "correlations_every", _count),
-    "correlation_max_distance": (None, "correlations_max_d", lambda v: v),
-    # the joint histogram strategy x reputation bin (reputation_history_bins bins over R_min .. R_max)
-    # and, with reputation_max_distance not None, the pair sums of the int8 reputation plane at the
-    # distances 0 .. reputation_max_distance (REPUTATION_DATASETS)
-    "reputation_history_every": (0, "reputation_every", _count),
-    "reputation_history_bins": (20, "reputation_bins", int),
-    "reputation_max_distance": (None, "reputation_max_d", lambda v: v),
-}
+def record_options(values):
+    """(BatchEngine.run's record keyword arguments, the options of the drop-in alone) from option values (a
+    mapping; absent: default), converted and cross-checked kind by kind (ValueError)."""
+    run_kwargs, extras = {}, {}
+    for kind in KINDS.values():
+        v = {attr: conv(values.get(attr, default)) for attr, _kw, default, conv in kind.options}
+        kind.check_options(v)
+        for attr, kw, _default, _conv in kind.options:
+            (run_kwargs if kw else extras)[kw or attr] = v[attr]
+    return run_kwargs, extras
 
 
-# The strategy dwell record's options (dwell.py), class attributes of SPGG like the RECORD_OPTIONS but
-# a table of their own: the record is not one of records.KINDS.  name -> (default, conversion).
-# dwell_history_every = k > 0: track every agent's strategy changes from iteration 1 on and write the
-# DWELL_DATASETS (rows at t = 1, 1+k, ...) after the other records' datasets; dwell_fields: also the
-# per-agent DWELL_FIELD_DATASETS of the final state.
-DWELL_OPTIONS = {
-    "dwell_history_every": (0, _count),
-    "dwell_fields": (False, bool),
-}
-
-
-# The learned policy record's options (policy.py), class attributes of SPGG in a table of their own as
-# the dwell record's are.  name -> (default, conversion).  policy_history_every = k > 0: record the
-# policy field (classes by strategy and state, bonds, gap histograms) at t = 1, 1+k, ... on the device
-# and write the POLICY_DATASETS after the dwell datasets; _bins and _gap_range (a number g for (-g, g),
-# or a (lo, hi) pair): the gap histogram; policy_map_final: also the final state's per-agent map
-# class | strategy << 2 | state << 3 (uint8) as POLICY_MAP_DATASET.
-POLICY_OPTIONS = {
-    "policy_history_every": (0, _count),
-    "policy_history_bins": (32, int),
-    "policy_history_gap_range": (2.0, lambda v: v),
-    "policy_map_final": (False, bool),
-}
-
-
-# The payoff record's options (payoff.py), class attributes of SPGG in a table of their own as the policy
-# record's are.  name -> (default, conversion).  payoff_history_every = k > 0: record the payoff field
-# (the census of strategy x cooperating neighbours x group-cooperator total, and the bonds by their
-# difference in that total) at t = 1, 1+k, ... on the device and write the PAYOFF_DATASETS after the
-# policy datasets; payoff_max_distance not None: also the pair sums of K and c at the distances
-# 0 .. payoff_max_distance (PAYOFF_PAIRS_DATASET); payoff_map_final: also the final state's per-agent
-# map K | strategy << 5 | (m & 3) << 6 (uint8) as PAYOFF_MAP_DATASET.
-PAYOFF_OPTIONS = {
-    "payoff_history_every": (0, _count),
-    "payoff_max_distance": (None, lambda v: v),
-    "payoff_map_final": (False, bool),
-}
-
-
-# The pair-map record's options (pairmap.py), class attributes of SPGG in a table of their own as the
-# payoff record's are.  name -> (default, conversion).  pair_map_history_every = k > 0: record the 2-D pair
-# maps of the fields of pair_map_fields -- a tuple of (a, b) pairs of "coop" and "flip" -- at every
-# displacement up to pair_map_max_distance (None: min(L // 2, 32)) at t = 1, 1+k, ... on the device and
-# write pair_map_history_iters, one pair_map_<a>_<b>_history per pair and pair_map_max_distance after the
-# payoff datasets.
-PAIR_MAP_OPTIONS = {
-    "pair_map_history_every": (0, _count),
-    "pair_map_max_distance": (None, lambda v: v),
-    "pair_map_fields": ((("coop", "coop"),), lambda v: tuple(tuple(p) for p in v)),
-}
-
-
-def _tiled(v):
-    return v if isinstance(v, bool) else (int(v) if v else False)
-
-
-# The tiled cluster labelling's option, a class attribute of SPGG like the others in a table of its
-# own.  name -> (default, BatchEngine.run keyword argument, conversion).  cluster_history_tiled: False:
-# the in-run cluster record is written by the one-workgroup kernel (lattices up to side 200); True: by
-# spgg_clusters_tiled (any side) with the library's tile; an int: with that tile side (8 .. 200).  Needs
-# cluster_history_every > 0; the datasets are the same.
-CLUSTER_TILED_OPTIONS = {
-    "cluster_history_tiled": (False, "clusters_tiled", _tiled),
-}
-
-
-def cluster_tiled_run_kwargs(values):
-    """BatchEngine.run's clusters_tiled keyword argument from option values (a mapping; absent: default)."""
-    return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in CLUSTER_TILED_OPTIONS.items()}
-
-
-def dwell_option_values(values):
-    """(dwell_every, dwell_fields) from option values (a mapping; absent: default)."""
-    every, fields = (conv(values.get(name, default)) for name, (default, conv) in DWELL_OPTIONS.items())
-    if fields and not every:
-        raise ValueError("dwell_fields needs dwell_history_every > 0 (nothing is tracked otherwise)")
-    return every, fields
-
-
-def dwell_histories(eng, every, fields):
-    """write_datasets' dwell_hist of every replica of a run(dwell_every=every): the engine's
-    dwell_histories, with `fields` also the per-agent fields of the final state; None without."""
-    if not every:
-        return None
-    hist = eng.dwell_histories()
-    if fields:
-        for k, h in enumerate(hist):
-            f = eng.dwell_fields(k)
-            h.update({name: f[key] for name, key in zip(DWELL_FIELD_DATASETS, ("flip_count", "strategy_age",
-                                                                               "cooperation_frequency"))})
-    return hist
-
-
-def policy_option_values(values):
-    """(BatchEngine.run's policy keyword arguments, policy_map_final) from option values (a mapping;
-    absent: default)."""
-    every, bins, gap_range, final = (conv(values.get(name, default)) for name, (default, conv) in POLICY_OPTIONS.items())
-    if final and not every:
-        raise ValueError("policy_map_final needs policy_history_every > 0 (nothing is recorded otherwise)")
-    return dict(policy_every=every, policy_bins=bins, policy_gap_range=gap_range), final
-
-
-def policy_histories(eng, run_kw, map_final):
-    """write_datasets' policy_hist of every replica of a run(**run_kw): the engine's policy_histories,
-    with map_final also the final state's map; None without the record."""
-    if not run_kw["policy_every"]:
-        return None
-    hist = eng.policy_histories()
-    if map_final:
-        for k, h in enumerate(hist):
-            h[POLICY_MAP_DATASET] = eng.policy_map(k)
-    return hist
-
-
-def payoff_option_values(values):
-    """(BatchEngine.run's payoff keyword arguments, payoff_map_final) from option values (a mapping;
-    absent: default)."""
-    every, max_d, final = (conv(values.get(name, default)) for name, (default, conv) in PAYOFF_OPTIONS.items())
-    if (final or max_d is not None) and not every:
-        raise ValueError("payoff_max_distance and payoff_map_final need payoff_history_every > 0 (nothing is "
-                         "recorded otherwise)")
-    return dict(payoff_every=every, payoff_max_d=max_d), final
-
-
-def payoff_histories(eng, run_kw, map_final):
-    """write_datasets' payoff_hist of every replica of a run(**run_kw): the engine's payoff_histories,
-    with map_final also the final state's map; None without the record."""
-    if not run_kw["payoff_every"]:
-        return None
-    hist = eng.payoff_histories()
-    if map_final:
-        for k, h in enumerate(hist):
-            h[PAYOFF_MAP_DATASET] = eng.payoff_map(k)
-    return hist
-
-
-def pair_map_option_values(values):
-    """BatchEngine.run's pair-map keyword arguments from option values (a mapping; absent: default)."""
-    every, max_d, fields = (conv(values.get(name, default)) for name, (default, conv) in PAIR_MAP_OPTIONS.items())
-    if max_d is not None and not every:
-        raise ValueError("pair_map_max_distance needs pair_map_history_every > 0 (nothing is recorded otherwise)")
-    return dict(pair_map_every=every, pair_map_max_d=max_d, pair_map_fields=field_pairs(fields))
-
-
-def pair_map_histories(eng, run_kw):
-    """write_datasets' pair_map_hist of every replica of a run(**run_kw): the engine's pair_map_histories;
-    None without the record."""
-    return eng.pair_map_histories() if run_kw["pair_map_every"] else None
-
-
-def record_run_kwargs(values):
-    """BatchEngine.run's record keyword arguments from option values (a mapping; absent: default)."""
-    return {kw: conv(values.get(name, default)) for name, (default, kw, conv) in RECORD_OPTIONS.items()}
+def record_histories(eng, run_kwargs, extras):
+    """kind name -> the per-replica histories of each record the run(**run_kwargs) took, with the final-state
+    datasets `extras` ask for, None for the others -- whose getter is not asked."""
+    out = {}
+    for name, kind in KINDS.items():
+        out[name] = getattr(eng, kind.getter)() if run_kwargs[kind.options[0][1]] > 0 else None
+        for k, h in enumerate(out[name] or ()):
+            h.update(kind.finals(eng, k, extras))
+    return out
 
 
 class SPGG:
     """Spatial Public Goods Game with RL, reputation and neighbor influence."""
 
     save_png = True  # strategy PNGs at snapshot iterations (spgg.py:552-559)
-    # (the RECORD_OPTIONS, DWELL_OPTIONS, CLUSTER_TILED_OPTIONS, POLICY_OPTIONS, PAYOFF_OPTIONS and PAIR_MAP_OPTIONS are class attributes too, set
-    # at their defaults below the class)
+    # (the RECORD_OPTIONS are class attributes too, set at their defaults below the class)
 
     def __init__(self, r=2, c=1, cost=0.5, K=0.1, L=50, iterations=1000,
                  num_of_strategies=2, population_type=0, S_in_one=None,
@@ -325,21 +171,11 @@ class SPGG:
         snapshots_dir = os.path.join(self.folder, 'plots', 'snapshots') if self.folder else 'snapshots'
         os.makedirs(snapshots_dir, exist_ok=True)
         try:
-            records = record_run_kwargs({name: getattr(self, name) for name in RECORD_OPTIONS})
-            dwell_every, dwell_fields = dwell_option_values({name: getattr(self, name) for name in DWELL_OPTIONS})
-            tiled = cluster_tiled_run_kwargs({name: getattr(self, name) for name in CLUSTER_TILED_OPTIONS})
-            policy_kw, policy_map = policy_option_values({name: getattr(self, name) for name in POLICY_OPTIONS})
-            payoff_kw, payoff_map = payoff_option_values({name: getattr(self, name) for name in PAYOFF_OPTIONS})
-            pair_map_kw = pair_map_option_values({name: getattr(self, name) for name in PAIR_MAP_OPTIONS})
-            eng.run(snapshots=True, png=self.save_png, dwell_every=dwell_every, **records, **tiled, **policy_kw,
-                    **payoff_kw, **pair_map_kw)
+            run_kwargs, extras = record_options({name: getattr(self, name) for name in RECORD_OPTIONS})
+            eng.run(snapshots=True, png=self.save_png, **run_kwargs)
             hist = eng.histories()[0]
             clusters = eng.cluster_sizes(0)   # labelled on the device (over many workgroups above side 200)
-            record_hists = {arg: h and h[0] for arg, h in record_histories(eng, records).items()}
-            dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
-            policy_hist = policy_histories(eng, policy_kw, policy_map)
-            payoff_hist = payoff_histories(eng, payoff_kw, payoff_map)
-            pair_map_hist = pair_map_histories(eng, pair_map_kw)
+            records = {name: h and h[0] for name, h in record_histories(eng, run_kwargs, extras).items()}
             Q, R, S = eng.final_state(0)
             tables = eng.final_tables(0) if kind == "double_qlearning" else None
             last = eng.last_iteration(0)
@@ -370,9 +206,7 @@ class SPGG:
         # the datasets last: the reference fills its file after the loop, so a write
         # error (duplicate tracked positions at L <= 2) leaves the state above in place
         write_datasets(filename, hist, snaps, S, R, self.R_min, self.R_max, self.track_positions,
-                       clusters=clusters, dwell_hist=dwell_hist and dwell_hist[0],
-                       policy_hist=policy_hist and policy_hist[0], payoff_hist=payoff_hist and payoff_hist[0],
-                       pair_map_hist=pair_map_hist and pair_map_hist[0], **record_hists)
+                       clusters=clusters, records=records)
 
         S_coop = (S == 0).astype(int)
         S_def = (S == 1).astype(int)
@@ -380,16 +214,6 @@ class SPGG:
 
 
 for _name, (_default, _kw, _conv) in RECORD_OPTIONS.items():
-    setattr(SPGG, _name, _default)
-for _name, (_default, _conv) in DWELL_OPTIONS.items():
-    setattr(SPGG, _name, _default)
-for _name, (_default, _kw, _conv) in CLUSTER_TILED_OPTIONS.items():
-    setattr(SPGG, _name, _default)
-for _name, (_default, _conv) in POLICY_OPTIONS.items():
-    setattr(SPGG, _name, _default)
-for _name, (_default, _conv) in PAYOFF_OPTIONS.items():
-    setattr(SPGG, _name, _default)
-for _name, (_default, _conv) in PAIR_MAP_OPTIONS.items():
     setattr(SPGG, _name, _default)
 
 
@@ -400,55 +224,15 @@ HISTORY_DATASETS = ("it_records_final", "epsilon_history_final", "rep_avg_histor
                     "reputation_reward_ratio", "avg_reward_C_history", "avg_reward_D_history")
 
 
-CLUSTER_DATASETS = ("cluster_history_iters", "cluster_count_history", "largest_cluster_history",
-                    "cd_bond_history")
-
-
-CORRELATION_DATASETS = ("correlation_history_iters", "pair_count_rows_history", "pair_count_cols_history")
-
-
-# the last four only with reputation_max_distance set (BatchEngine.reputation_histories)
-REPUTATION_DATASETS = ("reputation_history_iters", "reputation_hist_history", "reputation_bin_edges",
-                       "reputation_sum_history", "reputation_pair_rows_history", "reputation_pair_cols_history",
-                       "reputation_unit")
-OPTIONAL_DATASETS = REPUTATION_DATASETS[3:]
-FLOAT_DATASETS = ("reputation_bin_edges", "reputation_unit")   # the other record datasets are int64
-
-
-# per record kind: run()'s keyword that switches it on, the engine's getter, write_datasets' keyword, its datasets
-RECORD_KINDS = (("clusters_every", "cluster_histories", "cluster_hist", CLUSTER_DATASETS),
-                ("correlations_every", "correlation_histories", "correlation_hist", CORRELATION_DATASETS),
-                ("reputation_every", "reputation_histories", "reputation_hist", REPUTATION_DATASETS))
-
-
-def record_histories(eng, run_kwargs):
-    """write_datasets' keyword -> the engine's per-replica histories of each record the run took
-    (run_kwargs: record_run_kwargs' result), None for the others -- whose getter is not asked."""
-    return {arg: getattr(eng, getter)() if run_kwargs[on] > 0 else None for on, getter, arg, _names in RECORD_KINDS}
-
-
-def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None,
-                   cluster_hist=None, correlation_hist=None, reputation_hist=None, dwell_hist=None, policy_hist=None,
-                   payoff_hist=None, pair_map_hist=None):
+def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, clusters=None, records=None):
     """The dataset layout `SPGG.run` writes (spgg.py:594-633): snapshots, the
     per-iteration histories, the never-filled tracked-position Q datasets and
     the final state.  Shared by SPGG.run and the batched sweep runner.
 
     clusters: the final cluster sizes (BatchEngine.cluster_sizes) instead of labelling S on the
-    host here; cluster_hist: the in-run cluster record (BatchEngine.cluster_histories), written
-    as the CLUSTER_DATASETS after the reference's own; correlation_hist: the in-run pair-count
-    record (BatchEngine.correlation_histories), written as the CORRELATION_DATASETS after those;
-    reputation_hist: the in-run reputation record (BatchEngine.reputation_histories), written as
-    the REPUTATION_DATASETS it holds after those; dwell_hist: the in-run strategy dwell record
-    (BatchEngine.dwell_histories), written as the DWELL_DATASETS after those, then the
-    DWELL_FIELD_DATASETS it holds (int64; cooperation_frequency_final f64); policy_hist: the in-run
-    policy record (BatchEngine.policy_histories), written as the POLICY_DATASETS after those (int64;
-    policy_gap_bin_edges f64), then POLICY_MAP_DATASET (uint8) if it holds it; payoff_hist: the in-run
-    payoff record (BatchEngine.payoff_histories), written as the PAYOFF_DATASETS after those (int64;
-    payoff_values f64), then PAYOFF_PAIRS_DATASET (int64) and PAYOFF_MAP_DATASET (uint8) if it holds them;
-    pair_map_hist: the in-run pair-map record (BatchEngine.pair_map_histories), written after those:
-    pair_map_history_iters, one pair_map_<a>_<b>_history (rows, D + 1, 2 D + 1) per field pair and the scalar
-    pair_map_max_distance, all int64.
+    host here; records: kind name -> one replica's in-run record (record_histories) or None, written after the
+    reference's own datasets, the kinds in the order of records.KINDS and each kind's datasets in the order,
+    with the dtype (int64, float64 or uint8), of its `files` -- an optional one only if the record holds it.
     The defaults write the reference's file."""
     with open_writer(filename) as data_file:
         for i in sorted(snaps):
@@ -481,31 +265,11 @@ def write_datasets(filename, hist, snaps, S, R, R_min, R_max, track_positions, c
         data_file.create_dataset("rep_bins_final", data=bins)
         data_file.create_dataset("cluster_sizes", data=cluster_sizes(S) if clusters is None
                                  else np.asarray(clusters, dtype=np.int64))
-        for (_on, _getter, _arg, names), h in zip(RECORD_KINDS, (cluster_hist, correlation_hist, reputation_hist)):
-            for name in names if h is not None else ():
-                if name in h or name not in OPTIONAL_DATASETS:
-                    data_file.create_dataset(name, data=np.asarray(
-                        h[name], dtype=np.float64 if name in FLOAT_DATASETS else np.int64))
-        for name in DWELL_DATASETS + DWELL_FIELD_DATASETS if dwell_hist is not None else ():
-            if name in dwell_hist or name in DWELL_DATASETS:
-                data_file.create_dataset(name, data=np.asarray(
-                    dwell_hist[name], dtype=np.float64 if name == "cooperation_frequency_final" else np.int64))
-        for name in POLICY_DATASETS if policy_hist is not None else ():
-            data_file.create_dataset(name, data=np.asarray(
-                policy_hist[name], dtype=np.float64 if name == "policy_gap_bin_edges" else np.int64))
-        if policy_hist is not None and POLICY_MAP_DATASET in policy_hist:
-            data_file.create_dataset(POLICY_MAP_DATASET, data=np.asarray(policy_hist[POLICY_MAP_DATASET], dtype=np.uint8))
-        for name in PAYOFF_DATASETS if payoff_hist is not None else ():
-            data_file.create_dataset(name, data=np.asarray(
-                payoff_hist[name], dtype=np.float64 if name == "payoff_values" else np.int64))
-        if payoff_hist is not None and PAYOFF_PAIRS_DATASET in payoff_hist:
-            data_file.create_dataset(PAYOFF_PAIRS_DATASET, data=np.asarray(payoff_hist[PAYOFF_PAIRS_DATASET], dtype=np.int64))
-        if payoff_hist is not None and PAYOFF_MAP_DATASET in payoff_hist:
-            data_file.create_dataset(PAYOFF_MAP_DATASET, data=np.asarray(payoff_hist[PAYOFF_MAP_DATASET], dtype=np.uint8))
-        if pair_map_hist is not None:
-            maps = [name for name in pair_map_hist if name not in (PAIR_MAP_ITERS_DATASET, PAIR_MAP_DISTANCE_DATASET)]
-            for name in [PAIR_MAP_ITERS_DATASET, *maps, PAIR_MAP_DISTANCE_DATASET]:
-                data_file.create_dataset(name, data=np.asarray(pair_map_hist[name], dtype=np.int64))
+        for name, kind in KINDS.items():
+            h = (records or {}).get(name)
+            for ds, dtype, optional in kind.file_datasets(h) if h is not None else ():
+                if ds in h or not optional:
+                    data_file.create_dataset(ds, data=np.asarray(h[ds], dtype=dtype))
 
 
 def track_positions(L):

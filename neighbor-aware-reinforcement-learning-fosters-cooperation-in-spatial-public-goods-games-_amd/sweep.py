@@ -188,8 +188,7 @@ def run_one_experiment(params: Tuple, **model_overrides) -> Tuple[Tuple, Tuple[f
     folder = get_folder_name(*p8)
     make_folders(folder)
     kw = dict(RUNNER_MODEL, **model_overrides)
-    records = dict(pop_record_options(kw), **pop_dwell_options(kw), **pop_cluster_tiled_options(kw),
-                   **pop_policy_options(kw), **pop_payoff_options(kw), **pop_pair_map_options(kw))
+    records = pop_record_options(kw)
     spgg = SPGG(r=r, alpha=alpha, influence_factor=kappa, use_second_order=so,
                 reward_weight_payoff=w_p, rep_gain_C=gain, state_representation=state,
                 algorithm=algorithm, **kw)
@@ -204,45 +203,10 @@ def run_one_experiment(params: Tuple, **model_overrides) -> Tuple[Tuple, Tuple[f
 
 def pop_record_options(kw):
     """Take the in-run record options (spgg.RECORD_OPTIONS: class attributes of the drop-in, not
-    constructor arguments nor RUNNER_MODEL keys) out of the model overrides kw: name -> value,
+    constructor arguments nor RUNNER_MODEL keys) out of the model overrides kw: name -> converted value,
     absent ones at their defaults."""
     from .spgg import RECORD_OPTIONS
     return {name: conv(kw.pop(name, default)) for name, (default, _run_kw, conv) in RECORD_OPTIONS.items()}
-
-
-def pop_dwell_options(kw):
-    """Take the strategy dwell record's options (spgg.DWELL_OPTIONS) out of the model overrides kw
-    the same way."""
-    from .spgg import DWELL_OPTIONS
-    return {name: conv(kw.pop(name, default)) for name, (default, conv) in DWELL_OPTIONS.items()}
-
-
-def pop_cluster_tiled_options(kw):
-    """Take the tiled cluster labelling's option (spgg.CLUSTER_TILED_OPTIONS) out of the model
-    overrides kw the same way."""
-    from .spgg import CLUSTER_TILED_OPTIONS
-    return {name: conv(kw.pop(name, default)) for name, (default, _run_kw, conv) in CLUSTER_TILED_OPTIONS.items()}
-
-
-def pop_policy_options(kw):
-    """Take the learned policy record's options (spgg.POLICY_OPTIONS) out of the model overrides kw
-    the same way."""
-    from .spgg import POLICY_OPTIONS
-    return {name: conv(kw.pop(name, default)) for name, (default, conv) in POLICY_OPTIONS.items()}
-
-
-def pop_payoff_options(kw):
-    """Take the payoff record's options (spgg.PAYOFF_OPTIONS) out of the model overrides kw the same
-    way."""
-    from .spgg import PAYOFF_OPTIONS
-    return {name: conv(kw.pop(name, default)) for name, (default, conv) in PAYOFF_OPTIONS.items()}
-
-
-def pop_pair_map_options(kw):
-    """Take the pair-map record's options (spgg.PAIR_MAP_OPTIONS) out of the model overrides kw the same
-    way."""
-    from .spgg import PAIR_MAP_OPTIONS
-    return {name: conv(kw.pop(name, default)) for name, (default, conv) in PAIR_MAP_OPTIONS.items()}
 
 
 def _replica(p8, kw, seed):
@@ -268,17 +232,10 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
     `np.random.seed()` (spgg.py:98)."""
     import torch
     from .engine import BatchEngine, reference_init
-    from .spgg import (_write_pngs, cluster_tiled_run_kwargs, dwell_histories, dwell_option_values, pair_map_histories,
-                       pair_map_option_values, payoff_histories, payoff_option_values, policy_histories,
-                       policy_option_values, record_histories, record_run_kwargs, track_positions, write_datasets)
+    from .spgg import _write_pngs, record_histories, record_options, track_positions, write_datasets
     from .algorithms import canonical_name
     kw = dict(RUNNER_MODEL, **model_overrides)
-    records = record_run_kwargs(pop_record_options(kw))
-    dwell_every, dwell_fields = dwell_option_values(pop_dwell_options(kw))
-    tiled = cluster_tiled_run_kwargs(pop_cluster_tiled_options(kw))
-    policy_kw, policy_map = policy_option_values(pop_policy_options(kw))
-    payoff_kw, payoff_map = payoff_option_values(pop_payoff_options(kw))
-    pair_map_kw = pair_map_option_values(pop_pair_map_options(kw))
+    run_kwargs, extras = record_options(pop_record_options(kw))
     L, iters = int(kw["L"]), int(kw["iterations"])
     p8s = [unpack(p) for p in param_list]
     seeds = list(seeds) if seeds is not None else [None] * len(p8s)
@@ -301,24 +258,16 @@ def run_batch(param_list: Sequence[Tuple], seeds: Optional[Sequence[Optional[int
         eng = BatchEngine(L, max(iters, 1), reps, use_second_order=so, state_representation=state,
                           rng="mt19937", init=inits, algorithm=alg)
         try:
-            eng.run(snapshots=True, png=save_png, progress=progress, dwell_every=dwell_every, **records, **tiled,
-                    **policy_kw, **payoff_kw, **pair_map_kw)
+            eng.run(snapshots=True, png=save_png, progress=progress, **run_kwargs)
             hist = eng.histories()
-            record_hists = record_histories(eng, records)
-            dwell_hist = dwell_histories(eng, dwell_every, dwell_fields)
-            policy_hist = policy_histories(eng, policy_kw, policy_map)
-            payoff_hist = payoff_histories(eng, payoff_kw, payoff_map)
-            pair_map_hist = pair_map_histories(eng, pair_map_kw)
+            records = record_histories(eng, run_kwargs, extras)
             for k, i in enumerate(idx):
                 folder = get_folder_name(*p8s[i])
                 make_folders(folder)
                 _q, R, S = eng.final_state(k)
                 write_datasets(os.path.join(folder, "data", "experiment_data.h5"), hist[k], eng.snapshots[k],
                                S, R, kw["R_min"], kw["R_max"], track_positions(L),
-                               clusters=eng.cluster_sizes(k), dwell_hist=dwell_hist and dwell_hist[k],
-                               policy_hist=policy_hist and policy_hist[k], payoff_hist=payoff_hist and payoff_hist[k],
-                               pair_map_hist=pair_map_hist and pair_map_hist[k],
-                               **{arg: h and h[k] for arg, h in record_hists.items()})
+                               clusters=eng.cluster_sizes(k), records={name: h and h[k] for name, h in records.items()})
                 if save_png and eng.png_frames[k]:
                     _write_pngs(eng.png_frames[k], os.path.join(folder, "plots", "snapshots"))
                 coop = float(np.sum(S == 0)) / (L * L)

@@ -1,9 +1,9 @@
-"""The oracle's side of the five in-run device records (clusters, correlations, reputation, dwell,
-policy): one oracle run per replica of a tests/_params.Batch gives S_t and R_t at the start of every
+"""The oracle's side of the seven in-run device records (clusters, correlations, reputation, dwell,
+policy, payoff, pair_map): one oracle run per replica of a tests/_params.Batch gives S_t and R_t at the start of every
 iteration, the policy rows (tests/_policy's, from the same run), the final state, the stop iteration
 and (MT19937) the RandomState after the run; the expected datasets of a record are the existing host
 models applied to those planes on the record's schedule.  The device has no part in any of it, and no
-record is modelled here: tests/_clusters, _correlations, _reputation, _dwell and _policy are.
+record is modelled here: tests/_clusters, _correlations, _reputation, _dwell, _policy, _payoff and _pairmap are.
 NumPy only; no GPU, no engine is built (assert_all / assert_run read a finished one)."""
 import dataclasses
 import functools
@@ -13,25 +13,30 @@ import numpy as np
 from oracle import philox as PH
 from oracle import spgg_oracle as O
 from spgg_amd import dwell as DW
+from spgg_amd.pairmap import host_fields, host_pair_map
+from spgg_amd.payoff import host_payoff_census, host_payoff_pairs
 from spgg_amd.policy import host_policy_record, policy_bin_edges, split_row
 from spgg_amd.records import host_pair_counts, reputation_bin_edges
 from tests import _clusters as CL
 from tests import _correlations as CO
 from tests import _dwell as DM
+from tests import _pairmap as PMT
 from tests import _params as P
+from tests import _payoff as PFT
 from tests import _policy as PO
 from tests import _reputation as RP
 from tests._philox import check_final
 
-KINDS = ("clusters", "correlations", "reputation", "dwell", "policy")
+KINDS = ("clusters", "correlations", "reputation", "dwell", "policy", "payoff", "pair_map")
 GETTERS = dict(clusters="cluster_histories", correlations="correlation_histories", reputation="reputation_histories",
-               dwell="dwell_histories", policy="policy_histories")
+               dwell="dwell_histories", policy="policy_histories", payoff="payoff_histories", pair_map="pair_map_histories")
 # the settings of tests/test_gpu_records_layouts.py: pairwise different periods, none of which divides or is divided by
 # the turn lengths 7 (SPGG_CHUNK of the waves layout) and 8 (SPGG_ENQ_CHUNK of the no_interleave layout) -- which
 # 2, 4 and 7 would; tests/test_records_layouts_cpu.py holds what the schedule has to satisfy
 SETTINGS = dict(clusters=dict(every=3, periodic=False, tiled=False), correlations=dict(every=6, max_d=3),
                 reputation=dict(every=5, bins=9, max_d=2), dwell=dict(every=9),
-                policy=dict(every=11, bins=PO.BINS, gap_range=PO.GAP_RANGE))
+                policy=dict(every=11, bins=PO.BINS, gap_range=PO.GAP_RANGE), payoff=dict(every=13, max_d=2),
+                pair_map=dict(every=10, max_d=2, fields=(("coop", "coop"), ("flip", "coop"))))
 
 
 def settings(t0=1, scale=1, only=KINDS, **over):
@@ -61,6 +66,11 @@ def run_kwargs(s):
     if "policy" in s:
         p = s["policy"]
         kw.update(policy_every=p["every"], policy_bins=p["bins"], policy_gap_range=p["gap_range"])
+    if "payoff" in s:
+        kw.update(payoff_every=s["payoff"]["every"], payoff_max_d=s["payoff"]["max_d"])
+    if "pair_map" in s:
+        m = s["pair_map"]
+        kw.update(pair_map_every=m["every"], pair_map_max_d=m["max_d"], pair_map_fields=m["fields"])
     return kw
 
 
@@ -166,8 +176,8 @@ def reputation_row(e, S, R, s):
 
 
 def kind_row(e, kind, s, t):
-    """The row of `kind` the models give on the planes of iteration t, flattened (dwell and policy, which
-    are no function of one pair of planes: the row of iteration t)."""
+    """The row of `kind` the models give on the planes of iteration t, flattened (not of dwell and policy, which
+    are no function of the planes of one iteration)."""
     if kind == "clusters":
         return clusters_row(e.S[t], s)
     if kind == "correlations":
@@ -175,6 +185,12 @@ def kind_row(e, kind, s, t):
     if kind == "reputation":
         h, r = reputation_row(e, e.S[t], e.R[t], s)
         return h.ravel() if r is None else np.concatenate([h.ravel(), r])
+    if kind == "payoff":
+        pairs = [] if s["max_d"] is None else [host_payoff_pairs(e.S[t], s["max_d"])]
+        return np.concatenate([host_payoff_census(e.S[t])[0]] + pairs)
+    if kind == "pair_map":
+        f = host_fields(PMT.oracle_bytes(e, t), t)
+        return np.concatenate([host_pair_map(f[a], f[b], s["max_d"]).ravel() for a, b in s["fields"]])
     raise ValueError(kind)
 
 
@@ -215,6 +231,10 @@ def datasets(e, kind, s, t0=1):
         counts, bonds, gaps = split_row(rows, s["bins"])
         return dict(policy_history_iters=its, policy_count_history=counts, policy_bond_history=bonds,
                     policy_gap_hist_history=gaps, policy_gap_bin_edges=policy_bin_edges(s["gap_range"], s["bins"]))
+    if kind == "payoff":
+        return PFT.datasets(e, s["every"], s["max_d"], t0)
+    if kind == "pair_map":
+        return PMT.datasets(e, s["every"], s["max_d"], s["fields"], t0)
     raise ValueError(kind)
 
 
@@ -382,7 +402,7 @@ LAYOUTS = {
                     streams=6, env=dict(SPGG_CACHE_MB="budget", SPGG_CHUNK="7")),
     "retired": Layout(retired_batch, settings(scale=8), streams=3, chunk=RETIRED_CHUNK, absorbing=True, sparse_policy=True),
     "persistent": Layout(lambda rng: P.batch_f(60)._replace(rng=rng),
-                         settings(only=("clusters", "correlations", "reputation"), clusters=dict(every=3),
+                         settings(only=("clusters", "correlations", "reputation", "payoff", "pair_map"), clusters=dict(every=3),
                                   correlations=dict(every=4), reputation=dict(every=7)),
                          env=dict(SPGG_PERSIST="1", SPGG_APT="2"), chunk=5),
     "tiled_clusters": Layout(_b6, settings(clusters=dict(tiled=8, periodic=True))),

@@ -48,7 +48,7 @@ def test_write_datasets_takes_the_engine_arrays(tmp_path, monkeypatch):
     clusters = np.array([7, 1, 3], dtype=np.int32)   # (any integer dtype in: int64 out, as the host's)
     hist = dict(cluster_history_iters=np.array([1, 4, 7]), cluster_count_history=np.array([5, 4, 3], dtype=np.int32),
                 largest_cluster_history=np.array([9, 10, 11]), cd_bond_history=np.array([40, 38, 30]))
-    got = _write(c, tmp_path, "b.npz", clusters=clusters, cluster_hist=hist)
+    got = _write(c, tmp_path, "b.npz", clusters=clusters, records=dict(clusters=hist))
     assert got["cluster_sizes"].dtype == np.int64 and np.array_equal(got["cluster_sizes"], clusters)
     assert set(spgg.CLUSTER_DATASETS) == set(hist)
     for k, v in hist.items():

@@ -139,18 +139,17 @@ def test_kernel_resources():
 
 
 def test_option_tables():
-    """The tiled option lives in a table of its own: RECORD_OPTIONS and DWELL_OPTIONS keep their entries."""
-    assert list(spgg.CLUSTER_TILED_OPTIONS) == ["cluster_history_tiled"]
-    assert len(spgg.RECORD_OPTIONS) == 7 and "cluster_history_tiled" not in spgg.RECORD_OPTIONS
-    assert "cluster_history_tiled" not in spgg.DWELL_OPTIONS
+    """The tiled option through the one entry point: an option of the clusters kind (the table itself:
+    tests/test_records_cpu.py)."""
+    assert [o[0] for o in records.Clusters.options][2] == "cluster_history_tiled"
     assert spgg.SPGG.cluster_history_tiled is False
-    assert spgg.cluster_tiled_run_kwargs({}) == {"clusters_tiled": False}
-    assert spgg.cluster_tiled_run_kwargs({"cluster_history_tiled": True}) == {"clusters_tiled": True}
-    assert spgg.cluster_tiled_run_kwargs({"cluster_history_tiled": 8}) == {"clusters_tiled": 8}
+    assert spgg.record_options({})[0]["clusters_tiled"] is False
+    assert spgg.record_options({"cluster_history_tiled": True})[0]["clusters_tiled"] is True
+    assert spgg.record_options({"cluster_history_tiled": 8})[0]["clusters_tiled"] == 8
     kw = dict(L=16, cluster_history_tiled=16, cluster_history_every=5)
-    assert sweep.pop_cluster_tiled_options(kw) == {"cluster_history_tiled": 16}
-    assert kw == dict(L=16, cluster_history_every=5)
-    assert sweep.pop_cluster_tiled_options({}) == {"cluster_history_tiled": False}
+    got = sweep.pop_record_options(kw)
+    assert (got["cluster_history_tiled"], got["cluster_history_every"]) == (16, 5) and kw == dict(L=16)
+    assert sweep.pop_record_options({})["cluster_history_tiled"] is False
 
 
 def test_validation_of_clusters_tiled():

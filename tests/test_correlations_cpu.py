@@ -150,7 +150,7 @@ def test_write_datasets_takes_the_correlation_record(tmp_path, monkeypatch):
                 pair_count_rows_history=np.arange(10, dtype=np.int32).reshape(2, 5),
                 pair_count_cols_history=np.arange(10, 20).reshape(2, 5))
     assert set(spgg.CORRELATION_DATASETS) == set(hist)
-    got = write("a.npz", correlation_hist=hist)
+    got = write("a.npz", records=dict(correlations=hist))
     base = write("b.npz")
     assert set(got) - set(base) == set(hist) and sorted(base) == sorted(c.datasets)
     for k, v in hist.items():
@@ -220,8 +220,8 @@ def test_sweep_pops_the_overrides(tmp_path, monkeypatch):
                  correlation_history_every=2, correlation_max_distance=3)
     assert seen["run"]["correlations_every"] == 2 and seen["run"]["correlations_max_d"] == 3
     assert seen["run"]["clusters_every"] == 0 and seen.pop("asked")
-    assert [w["correlation_hist"] for w in written] == [dict(marker=0), dict(marker=1)]
+    assert [w["records"]["correlations"] for w in written] == [dict(marker=0), dict(marker=1)]
     written.clear()
     SW.run_batch([params], seeds=[1], save_png=False, verbose=False, L=8, iterations=3)
     assert seen["run"]["correlations_every"] == 0 and seen["run"]["correlations_max_d"] is None
-    assert "asked" not in seen and written[0]["correlation_hist"] is None
+    assert "asked" not in seen and written[0]["records"]["correlations"] is None

@@ -101,21 +101,18 @@ def test_abi_still_v19_with_the_four_entry_points():
 
 
 def test_option_tables():
-    assert {n: d for n, (d, _conv) in spgg.DWELL_OPTIONS.items()} == dict(dwell_history_every=0, dwell_fields=False)
+    """The dwell options through the one entry point (the table itself: tests/test_records_cpu.py)."""
+    def values(**v):
+        run_kw, extras = spgg.record_options(v)
+        return run_kw["dwell_every"], extras["dwell_fields"]
+
     assert spgg.SPGG.dwell_history_every == 0 and spgg.SPGG.dwell_fields is False
-    # the record is not a fourth kind: the three tables of the in-run records are what they were
-    assert list(records.KINDS) == ["clusters", "correlations", "reputation"]
-    assert len(spgg.RECORD_OPTIONS) == 7 and not [n for n in spgg.RECORD_OPTIONS if "dwell" in n]
-    assert [k[0] for k in spgg.RECORD_KINDS] == ["clusters_every", "correlations_every", "reputation_every"]
-    assert sorted(spgg.record_run_kwargs({})) == sorted(
-        ["clusters_every", "clusters_periodic", "correlations_every", "correlations_max_d", "reputation_every",
-         "reputation_bins", "reputation_max_d"])
-    assert issubclass(dwell.Dwell, records.Record) and dwell.Dwell not in records.KINDS.values()
-    assert spgg.dwell_option_values({}) == (0, False)
-    assert spgg.dwell_option_values(dict(dwell_history_every="4", dwell_fields=1)) == (4, True)
-    assert spgg.dwell_option_values(dict(dwell_history_every=None)) == (0, False)
-    with pytest.raises(ValueError):
-        spgg.dwell_option_values(dict(dwell_fields=True))
+    assert issubclass(dwell.Dwell, records.Record) and records.KINDS["dwell"] is dwell.Dwell
+    assert values() == (0, False)
+    assert values(dwell_history_every="4", dwell_fields=1) == (4, True)
+    assert values(dwell_history_every=None) == (0, False)
+    with pytest.raises(ValueError, match="dwell_fields needs dwell_history_every > 0"):
+        values(dwell_fields=True)
     rec = dwell.Dwell(7, 3, 40)
     assert (rec.every, rec.t0, rec.rows, rec.key) == (7, 3, 6, (7,)) and rec.iters(20).tolist() == [3, 10, 17]
 
@@ -145,7 +142,8 @@ def test_sweep_pops_the_options(tmp_path, monkeypatch):
     SW.run_one_experiment(params, L=8, iterations=3)
     assert seen["attrs"] == (0, False, 0)
     kw = dict(L=8, dwell_history_every=2)
-    assert SW.pop_dwell_options(kw) == dict(dwell_history_every=2, dwell_fields=False) and kw == dict(L=8)
+    got = SW.pop_record_options(kw)
+    assert (got["dwell_history_every"], got["dwell_fields"]) == (2, False) and kw == dict(L=8)
 
     class FakeEngine:
         def __init__(self, L, iterations, replicas, **kw):
@@ -180,14 +178,14 @@ def test_sweep_pops_the_options(tmp_path, monkeypatch):
     SW.run_batch([params, params], seeds=[1, 2], save_png=False, verbose=False, L=8, iterations=3,
                  dwell_history_every=2, dwell_fields=True)
     assert seen["run"]["dwell_every"] == 2 and seen["run"]["reputation_every"] == 0
-    assert [w["dwell_hist"] for w in written] == [
+    assert [w["records"]["dwell"] for w in written] == [
         dict(marker=k, flip_count_final=k, strategy_age_final=10 + k, cooperation_frequency_final=0.5) for k in (0, 1)]
     written.clear()
     SW.run_batch([params], seeds=[1], save_png=False, verbose=False, L=8, iterations=3, dwell_history_every=3)
-    assert written[0]["dwell_hist"] == dict(marker=0)
+    assert written[0]["records"]["dwell"] == dict(marker=0)
     written.clear()
     SW.run_batch([params], seeds=[1], save_png=False, verbose=False, L=8, iterations=3)
-    assert seen["run"]["dwell_every"] == 0 and written[0]["dwell_hist"] is None
+    assert seen["run"]["dwell_every"] == 0 and written[0]["records"]["dwell"] is None
 
 
 def test_write_datasets_takes_the_dwell_record(tmp_path, monkeypatch):
@@ -215,9 +213,9 @@ def test_write_datasets_takes_the_dwell_record(tmp_path, monkeypatch):
     assert tuple(final) == dwell.DWELL_FIELD_DATASETS
     base = write("b.npz")
     assert sorted(base) == sorted(c.datasets)
-    got = write("a.npz", dwell_hist=hist)
+    got = write("a.npz", records=dict(dwell=hist))
     assert set(got) - set(base) == set(hist)
-    got = write("c.npz", dwell_hist=dict(hist, **final))
+    got = write("c.npz", records=dict(dwell=dict(hist, **final)))
     assert set(got) - set(base) == set(hist) | set(final)
     shapes = dict(dwell_history_iters=(3,), dwell_ref_iteration=(), persistence_history=(3, 2),
                   autocorrelation_history=(3, 3), flip_total_history=(3,), cooperator_time_history=(3,),

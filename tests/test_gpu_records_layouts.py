@@ -1,13 +1,13 @@
-"""The five in-run device records (clusters, correlations, reputation, dwell, policy), armed together,
-under every launch layout of BatchEngine.step: one group, a run that starts late, resident groups
-through spgg_step_groups and through one spgg_step call per group (SPGG_INTERLEAVE=0), cache-blocked
-waves on shared streams, groups retired mid-run (SPGG_SKIP_DEAD), persistent launches, and the tiled
-cluster kernel beside the other four.
+"""The seven in-run device records (clusters, correlations, reputation, dwell, policy, payoff, pair_map),
+armed together, under every launch layout of BatchEngine.step: one group, a run that starts late, resident
+groups through spgg_step_groups and through one spgg_step call per group (SPGG_INTERLEAVE=0), cache-blocked
+waves on shared streams, groups retired mid-run (SPGG_SKIP_DEAD), persistent launches (the five kinds that
+are allowed there), and the tiled cluster kernel beside the other six.
 
 Every expectation comes from one oracle run per replica (tests/_observers.py): the existing host models
 on the oracle's S_t / R_t and tables, which the device had no part in.  Each case also holds the run
 itself to the oracle -- S, R, Q, the stop iteration and the MT19937 key bit for bit -- which is "the
-records do not disturb the run" for all five at once.  tests/test_records_layouts_cpu.py holds, on the
+records do not disturb the run" for all seven at once.  tests/test_records_layouts_cpu.py holds, on the
 oracle alone, that the batches are not absorbed away, that a record of the planes of iteration t - 1
 would differ, and that the periods interleave.  Integers and bit patterns, exact; no tolerance."""
 import time
@@ -19,7 +19,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import spgg_amd  # noqa: E402
-from spgg_amd import dwell as DW, policy as PL, spgg as SP  # noqa: E402
+from spgg_amd import dwell as DW, pairmap as PM, payoff as PF, policy as PL, spgg as SP  # noqa: E402
 from spgg_amd.engine import BatchEngine  # noqa: E402
 from spgg_amd.h5io import read_datasets  # noqa: E402
 from tests import _observers as OB  # noqa: E402
@@ -141,16 +141,22 @@ def test_dropin_writes_every_record_at_once(tmp_path):
     m.dwell_history_every, m.dwell_fields = s["dwell"]["every"], True
     m.policy_history_every, m.policy_history_bins = s["policy"]["every"], s["policy"]["bins"]
     m.policy_history_gap_range, m.policy_map_final = s["policy"]["gap_range"], True
+    m.payoff_history_every, m.payoff_max_distance, m.payoff_map_final = s["payoff"]["every"], s["payoff"]["max_d"], True
+    m.pair_map_history_every, m.pair_map_max_distance = s["pair_map"]["every"], s["pair_map"]["max_d"]
+    m.pair_map_fields = [list(p) for p in s["pair_map"]["fields"]]
     m.folder = str(tmp_path)
     fn = str(tmp_path / "experiment_data.h5")
     m.run(fn)
     ds = read_datasets(fn)
 
-    # every dataset of the five records, once, and no name shared between two kinds
+    # every dataset of the seven records, once, and no name shared between two kinds
     want = {kind: OB.datasets(e, kind, s[kind]) for kind in OB.KINDS}
+    maps = tuple(PM.dataset_name(a, b) for a, b in s["pair_map"]["fields"])
     names = dict(clusters=SP.CLUSTER_DATASETS, correlations=SP.CORRELATION_DATASETS, reputation=SP.REPUTATION_DATASETS,
-                 dwell=DW.DWELL_DATASETS, policy=PL.POLICY_DATASETS)
-    every = [n for kind in OB.KINDS for n in names[kind]] + list(DW.DWELL_FIELD_DATASETS) + [PL.POLICY_MAP_DATASET]
+                 dwell=DW.DWELL_DATASETS, policy=PL.POLICY_DATASETS, payoff=PF.PAYOFF_DATASETS + (PF.PAYOFF_PAIRS_DATASET,),
+                 pair_map=(PM.PAIR_MAP_ITERS_DATASET, PM.PAIR_MAP_DISTANCE_DATASET) + maps)
+    every = ([n for kind in OB.KINDS for n in names[kind]] + list(DW.DWELL_FIELD_DATASETS)
+             + [PL.POLICY_MAP_DATASET, PF.PAYOFF_MAP_DATASET])
     assert len(set(every)) == len(every) and set(every) <= set(ds), sorted(set(every) - set(ds))
     assert not set(every) & set(e.datasets)
     for kind in OB.KINDS:
@@ -167,6 +173,8 @@ def test_dropin_writes_every_record_at_once(tmp_path):
         assert ds[name].dtype == w.dtype and np.array_equal(ds[name], w.reshape(L, L)), name
     assert ds[PL.POLICY_MAP_DATASET].dtype == np.uint8
     assert np.array_equal(ds[PL.POLICY_MAP_DATASET], e.policy.planes[e.t_final])
+    assert ds[PF.PAYOFF_MAP_DATASET].dtype == np.uint8
+    assert np.array_equal(ds[PF.PAYOFF_MAP_DATASET], PF.host_payoff_census(e.S[e.t_final])[1])
 
     # the reference's own datasets: the oracle's.  The sums the step kernels reduce in another order than np.mean
     # (tests/test_gpu_parity.APPROX) are held by test_spgg_dropin_matches_reference, not here

@@ -226,27 +226,29 @@ def test_header_binding_and_exports_agree():
 
 def test_option_tables():
     from spgg_amd import spgg, sweep
-    assert list(spgg.PAIR_MAP_OPTIONS) == ["pair_map_history_every", "pair_map_max_distance", "pair_map_fields"]
-    others = (set(spgg.RECORD_OPTIONS) | set(spgg.DWELL_OPTIONS) | set(spgg.POLICY_OPTIONS) | set(spgg.CLUSTER_TILED_OPTIONS)
-              | set(spgg.PAYOFF_OPTIONS))
-    assert len(spgg.RECORD_OPTIONS) == 7 and not set(spgg.PAIR_MAP_OPTIONS) & others
-    for name, (default, _conv) in spgg.PAIR_MAP_OPTIONS.items():
-        assert getattr(spgg.SPGG, name) == default
+    """The pair-map options through the one entry point (the table itself: tests/test_records_cpu.py)."""
+    mine = ["pair_map_history_every", "pair_map_max_distance", "pair_map_fields"]
+
+    def values(v):
+        return {k: x for k, x in spgg.record_options(v)[0].items() if k.startswith("pair_map")}
+
+    assert [o[0] for o in PM.PairMap.options] == mine
     assert (spgg.SPGG.pair_map_history_every, spgg.SPGG.pair_map_max_distance, spgg.SPGG.pair_map_fields) == (0, None, (("coop", "coop"),))
     kw = dict(L=8, pair_map_history_every="3", pair_map_max_distance=2, pair_map_fields=[["coop", "coop"], ["flip", "coop"]], epsilon=0.2)
-    got = sweep.pop_pair_map_options(kw)
+    got = {k: v for k, v in sweep.pop_record_options(kw).items() if k in mine}
     assert got == dict(pair_map_history_every=3, pair_map_max_distance=2, pair_map_fields=(("coop", "coop"), ("flip", "coop")))
     assert kw == dict(L=8, epsilon=0.2)
-    assert sweep.pop_pair_map_options({}) == {k: v[0] for k, v in spgg.PAIR_MAP_OPTIONS.items()}
-    assert spgg.pair_map_option_values(got) == dict(pair_map_every=3, pair_map_max_d=2, pair_map_fields=(("coop", "coop"), ("flip", "coop")))
-    assert spgg.pair_map_option_values({}) == dict(pair_map_every=0, pair_map_max_d=None, pair_map_fields=(("coop", "coop"),))
-    for bad in (dict(pair_map_max_distance=2), dict(pair_map_history_every=2, pair_map_fields=(("coop", "state"),)),
+    assert {k: v for k, v in sweep.pop_record_options({}).items() if k in mine} == {o[0]: o[2] for o in PM.PairMap.options}
+    assert values(got) == dict(pair_map_every=3, pair_map_max_d=2, pair_map_fields=(("coop", "coop"), ("flip", "coop")))
+    assert values({}) == dict(pair_map_every=0, pair_map_max_d=None, pair_map_fields=(("coop", "coop"),))
+    with pytest.raises(ValueError, match="pair_map_max_distance needs pair_map_history_every > 0"):
+        values(dict(pair_map_max_distance=2))
+    for bad in (dict(pair_map_history_every=2, pair_map_fields=(("coop", "state"),)),
                 dict(pair_map_history_every=2, pair_map_fields=(("coop", "coop"), ("coop", "coop"))),
                 dict(pair_map_history_every=2, pair_map_fields=())):
-        with pytest.raises(ValueError):
-            spgg.pair_map_option_values(bad)
-    assert "pair_map" not in records.KINDS and issubclass(PM.PairMap, records.Record)
-    assert sorted(records.KINDS) == ["clusters", "correlations", "reputation"]
+        with pytest.raises(ValueError, match="pair_map_fields"):
+            values(bad)
+    assert records.KINDS["pair_map"] is PM.PairMap and issubclass(PM.PairMap, records.Record)
     assert PM.dataset_name("coop", "flip") == "pair_map_coop_flip_history"
 
 
@@ -318,7 +320,7 @@ def test_datasets_reach_the_sinks(tmp_path, monkeypatch):
         spgg.write_datasets(fn, hist, {}, S, Rn, -10, 10, [], clusters=np.zeros(0, dtype=np.int64))
         plain = list(h5io.read_datasets(fn))
         assert not set(ph) & set(plain)
-        spgg.write_datasets(fn, hist, {}, S, Rn, -10, 10, [], clusters=np.zeros(0, dtype=np.int64), pair_map_hist=ph)
+        spgg.write_datasets(fn, hist, {}, S, Rn, -10, 10, [], clusters=np.zeros(0, dtype=np.int64), records=dict(pair_map=ph))
         got = h5io.read_datasets(fn)
         for name, want in ph.items():
             assert got[name].dtype == np.int64, (sink, name)

@@ -260,23 +260,25 @@ def test_header_binding_and_exports_agree():
 
 def test_option_tables():
     from spgg_amd import spgg, sweep
-    assert list(spgg.PAYOFF_OPTIONS) == ["payoff_history_every", "payoff_max_distance", "payoff_map_final"]
-    others = set(spgg.RECORD_OPTIONS) | set(spgg.DWELL_OPTIONS) | set(spgg.POLICY_OPTIONS) | set(spgg.CLUSTER_TILED_OPTIONS)
-    assert len(spgg.RECORD_OPTIONS) == 7 and not set(spgg.PAYOFF_OPTIONS) & others
-    for name, (default, _conv) in spgg.PAYOFF_OPTIONS.items():
-        assert getattr(spgg.SPGG, name) == default
+    """The payoff options through the one entry point (the table itself: tests/test_records_cpu.py)."""
+    mine = ["payoff_history_every", "payoff_max_distance", "payoff_map_final"]
+
+    def values(v):
+        run_kw, extras = spgg.record_options(v)
+        return {k: x for k, x in run_kw.items() if k.startswith("payoff")}, extras["payoff_map_final"]
+
+    assert [o[0] for o in PF.Payoff.options] == mine
     assert (spgg.SPGG.payoff_history_every, spgg.SPGG.payoff_max_distance, spgg.SPGG.payoff_map_final) == (0, None, False)
     kw = dict(L=8, payoff_history_every="3", payoff_max_distance=2, payoff_map_final=1, epsilon=0.2)
-    got = sweep.pop_payoff_options(kw)
+    got = {k: v for k, v in sweep.pop_record_options(kw).items() if k in mine}
     assert got == dict(payoff_history_every=3, payoff_max_distance=2, payoff_map_final=True) and kw == dict(L=8, epsilon=0.2)
-    assert sweep.pop_payoff_options({}) == {k: v[0] for k, v in spgg.PAYOFF_OPTIONS.items()}
-    assert spgg.payoff_option_values(got) == (dict(payoff_every=3, payoff_max_d=2), True)
-    assert spgg.payoff_option_values({}) == (dict(payoff_every=0, payoff_max_d=None), False)
+    assert {k: v for k, v in sweep.pop_record_options({}).items() if k in mine} == {o[0]: o[2] for o in PF.Payoff.options}
+    assert values(got) == (dict(payoff_every=3, payoff_max_d=2), True)
+    assert values({}) == (dict(payoff_every=0, payoff_max_d=None), False)
     for bad in (dict(payoff_map_final=True), dict(payoff_max_distance=2)):
-        with pytest.raises(ValueError):
-            spgg.payoff_option_values(bad)
-    assert "payoff" not in records.KINDS and issubclass(PF.Payoff, records.Record)
-    assert sorted(records.KINDS) == ["clusters", "correlations", "reputation"]
+        with pytest.raises(ValueError, match="payoff_max_distance and payoff_map_final need payoff_history_every > 0"):
+            values(bad)
+    assert records.KINDS["payoff"] is PF.Payoff and issubclass(PF.Payoff, records.Record)
     assert PF.PAYOFF_DATASETS == ("payoff_history_iters", "payoff_census_history", "payoff_bond_history", "payoff_values")
 
 
@@ -320,7 +322,7 @@ def test_datasets_reach_both_sinks(tmp_path, monkeypatch):
         plain = list(h5io.read_datasets(fn))
         assert not set(full) & set(plain)
         for ph in (base, full):
-            spgg.write_datasets(fn, hist, {}, S, Rn, -10, 10, [], clusters=np.zeros(0, dtype=np.int64), payoff_hist=ph)
+            spgg.write_datasets(fn, hist, {}, S, Rn, -10, 10, [], clusters=np.zeros(0, dtype=np.int64), records=dict(payoff=ph))
             got = h5io.read_datasets(fn)
             for name, want in ph.items():
                 assert np.array_equal(got[name], want), (sink, name)

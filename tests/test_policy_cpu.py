@@ -134,26 +134,28 @@ def test_header_binding_and_exports_agree():
 
 def test_option_tables():
     from spgg_amd import spgg, sweep
-    assert list(spgg.POLICY_OPTIONS) == ["policy_history_every", "policy_history_bins", "policy_history_gap_range",
-                                         "policy_map_final"]
-    assert len(spgg.RECORD_OPTIONS) == 7 and not set(spgg.POLICY_OPTIONS) & set(spgg.RECORD_OPTIONS)
-    assert [k[0] for k in spgg.RECORD_KINDS] == ["clusters_every", "correlations_every", "reputation_every"]
-    for name, (default, _conv) in spgg.POLICY_OPTIONS.items():
-        assert getattr(spgg.SPGG, name) == default
+    """The policy options through the one entry point (the table itself: tests/test_records_cpu.py)."""
+    mine = ["policy_history_every", "policy_history_bins", "policy_history_gap_range", "policy_map_final"]
+
+    def values(v):
+        run_kw, extras = spgg.record_options(v)
+        return {k: x for k, x in run_kw.items() if k.startswith("policy")}, extras["policy_map_final"]
+
+    assert [o[0] for o in PL.Policy.options] == mine
     assert (spgg.SPGG.policy_history_every, spgg.SPGG.policy_history_bins, spgg.SPGG.policy_history_gap_range,
             spgg.SPGG.policy_map_final) == (0, 32, 2.0, False)
     kw = dict(L=8, policy_history_every="3", policy_history_bins=16, policy_map_final=1, epsilon=0.2)
-    got = sweep.pop_policy_options(kw)
+    got = {k: v for k, v in sweep.pop_record_options(kw).items() if k in mine}
     assert got == dict(policy_history_every=3, policy_history_bins=16, policy_history_gap_range=2.0, policy_map_final=True)
     assert kw == dict(L=8, epsilon=0.2)
-    assert sweep.pop_policy_options({}) == {k: v[0] for k, v in spgg.POLICY_OPTIONS.items()}
-    run_kw, final = spgg.policy_option_values(got)
+    assert {k: v for k, v in sweep.pop_record_options({}).items() if k in mine} == {o[0]: o[2] for o in PL.Policy.options}
+    run_kw, final = values(got)
     assert run_kw == dict(policy_every=3, policy_bins=16, policy_gap_range=2.0) and final is True
-    assert spgg.policy_option_values({}) == (dict(policy_every=0, policy_bins=32, policy_gap_range=2.0), False)
-    with pytest.raises(ValueError):
-        spgg.policy_option_values(dict(policy_map_final=True))
+    assert values({}) == (dict(policy_every=0, policy_bins=32, policy_gap_range=2.0), False)
+    with pytest.raises(ValueError, match="policy_map_final needs policy_history_every > 0"):
+        values(dict(policy_map_final=True))
     from spgg_amd import records
-    assert "policy" not in records.KINDS and issubclass(PL.Policy, records.Record)
+    assert records.KINDS["policy"] is PL.Policy and issubclass(PL.Policy, records.Record)
     assert PL.POLICY_DATASETS == ("policy_history_iters", "policy_count_history", "policy_bond_history",
                                   "policy_gap_hist_history", "policy_gap_bin_edges")
 
@@ -205,7 +207,7 @@ def test_datasets_reach_both_sinks(tmp_path, monkeypatch):
     for sink in ("npz",) + (("native",) if h5io.h5native.available() else ()):
         monkeypatch.setenv("SPGG_H5_SINK", sink)
         fn = str(tmp_path / f"{sink}.h5")
-        spgg.write_datasets(fn, hist, {}, S, Rn, -10, 10, [], clusters=np.zeros(0, dtype=np.int64), policy_hist=ph)
+        spgg.write_datasets(fn, hist, {}, S, Rn, -10, 10, [], clusters=np.zeros(0, dtype=np.int64), records=dict(policy=ph))
         got = h5io.read_datasets(fn)
         for name, want in ph.items():
             assert np.array_equal(got[name], want), (sink, name)

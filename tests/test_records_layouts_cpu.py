@@ -66,7 +66,8 @@ def test_the_schedule_interleaves(name):
     s, T = lay.settings, lay.batch("philox").T
     recs = _records(s, T)
     periods = [r.every for r in recs.values()]
-    assert len(set(periods)) == len(periods) >= 3, periods
+    assert len(set(periods)) == len(periods) == (5 if name == "persistent" else 7), periods      # (dwell and policy: not there)
+    assert set(recs) == set(OB.KINDS) - ({"dwell", "policy"} if name == "persistent" else set())
     due = {t: [k for k, r in recs.items() if t >= r.t0 and r.due(t)] for t in range(s["t0"], T + 1)}
     assert any(len(d) >= 3 for d in due.values())
     assert any(len(d) == 1 for d in due.values())

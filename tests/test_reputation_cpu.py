@@ -245,9 +245,9 @@ def test_write_datasets_takes_the_reputation_record(tmp_path, monkeypatch):
     assert set(spgg.REPUTATION_DATASETS) == set(hist) | set(pairs)
     base = write("b.npz")
     assert sorted(base) == sorted(c.datasets)
-    got = write("a.npz", reputation_hist=hist)
+    got = write("a.npz", records=dict(reputation=hist))
     assert set(got) - set(base) == set(hist)
-    got = write("c.npz", reputation_hist=dict(hist, **pairs))
+    got = write("c.npz", records=dict(reputation=dict(hist, **pairs)))
     assert set(got) - set(base) == set(hist) | set(pairs)
     for k, v in dict(hist, **pairs).items():
         want = np.float64 if k in ("reputation_bin_edges", "reputation_unit") else np.int64
@@ -316,9 +316,9 @@ def test_sweep_pops_the_overrides(tmp_path, monkeypatch):
     run = seen["run"]
     assert (run["reputation_every"], run["reputation_bins"], run["reputation_max_d"]) == (2, 9, 3)
     assert run["clusters_every"] == 0 and run["correlations_every"] == 0 and seen.pop("asked")
-    assert [w["reputation_hist"] for w in written] == [dict(marker=0), dict(marker=1)]
+    assert [w["records"]["reputation"] for w in written] == [dict(marker=0), dict(marker=1)]
     written.clear()
     SW.run_batch([params], seeds=[1], save_png=False, verbose=False, L=8, iterations=3)
     run = seen["run"]
     assert (run["reputation_every"], run["reputation_bins"], run["reputation_max_d"]) == (0, 20, None)
-    assert "asked" not in seen and written[0]["reputation_hist"] is None
+    assert "asked" not in seen and written[0]["records"]["reputation"] is None
