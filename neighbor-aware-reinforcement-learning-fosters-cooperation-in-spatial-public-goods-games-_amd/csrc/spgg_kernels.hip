@@ -819,6 +819,22 @@ __device__ __forceinline__ float td_update(const TileArgs& a, const PT& pg, int 
   }
 }
 
+// One agent's reward w_P * P + w_rep * rr (spgg.py:424-427), rr = 0.5 for a cooperating action and
+// 0 otherwise.  unit_w (workgroup-uniform: a scalar branch): w_P == 1 and w_rep == +0, where the
+// reward is P itself, bit for bit (step_impl, at the flag), and the select, the two products and
+// the sum are skipped.  UW: the instance has the flag.  (The empty asm keeps the general path
+// behind the branch: without it the compiler computes both and selects.)
+template <bool UW>
+__device__ __forceinline__ double reward_of(bool unit_w, double P, bool coop, double w_p, double w_rep) {
+  if constexpr (UW) {
+    if (unit_w) return P;
+    asm volatile("");
+  }
+  const double rr = coop ? 0.5 : 0.0;
+  const double wpp = w_p * P, wrr = w_rep * rr;
+  return wpp + wrr;
+}
+
 // The pending NI record of iteration t-1 RECOMPUTED in launch t (every operator but SARSA,
 // whose diagnostic select draws again, spgg.py:452): instead of storing max(0, max_diff) (f64)
 // and |alpha*td'| (f32) per agent in launch t-1 and loading them here (24 B per agent-step of a
@@ -827,10 +843,10 @@ __device__ __forceinline__ float td_update(const TileArgs& a, const PT& pg, int 
 // from them and the Q rows it holds (the table after the TD update of t-1, before its NI term)
 // the same two values, bit for bit (the same f64 operations on the same operands).
 template <bool M2>
-__device__ __forceinline__ double prev_max_diff(const double* rew, int ca, int w) {
+__device__ __forceinline__ double prev_max_diff(const double* rew, double r0, int ca, int w) {
   // spgg.py:486-489 restated as phase 2 computes it: max over the 4 / 12 offsets of
-  // rew[nb] - rew[ca] (max is exact and order-free on non-NaN, never -0 rewards), then max(0, .)
-  const double r0 = rew[ca];
+  // rew[nb] - r0, r0 = rew[ca] (max is exact and order-free on non-NaN, never -0 rewards), then
+  // max(0, .)
   constexpr int KN = M2 ? 12 : 4;
   const int nb[12] = {ca - w, ca + w, ca - 1, ca + 1, ca - 2 * w, ca + 2 * w, ca - 2, ca + 2,
                       ca - w - 1, ca - w + 1, ca + w - 1, ca + w + 1};
@@ -1056,6 +1072,9 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // iteration, which takes the row; the latency-bound two-per-thread kernels lose a wave of
   // occupancy to the held agent indices; the second-order kernels run at four waves already
   constexpr bool SLOT = !M2 && TWC > 0 && !DSTAGE && !PERSIST && APT == spgg_impl::apt_of(ALG) && ALG != ALG_DQ;
+  // the rewards of iteration t-1 per agent slot and ring cell instead of a loop over the region
+  // (below, after the plus-count planes): the slot-word kernels that recompute the NI record
+  constexpr bool PREV = SLOT && RECOMP;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   // XCD-aware placement: blocks b, b+8, b+16... share an XCD (round-robin
@@ -1296,6 +1315,14 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
                                         : kPayWord + 17 - min(tid - kParamWords, 11)));
   const spgg_rep_params& hp = hps;
   const double kappa = pg.kappa, w_p = pg.w_p, w_rep = pg.w_rep;
+  // Unit reward weights (SLOT; a scalar flag, as ni_on below: an f64 compare has no scalar form):
+  // w_P == 1 and w_rep == +0, every replica of a sweep at w_P = 1.  Then rew = P bit for bit and
+  // every reward site skips the rr select, both products and the sum: 1.0 * P == P; w_rep * rr is
+  // +0 for w_rep = +0 and rr in {0.5, 0}; and P + (+0) == P because P is never -0 (div_uniform of
+  // a tot - norm_min that is exactly zero gives +0: x - x is +0 in round-to-nearest).  The compare
+  // is true for w_rep = -0 too, where w_rep * rr is -0 and P + (-0) == P for every P.
+  bool unit_w = false;
+  if constexpr (SLOT) unit_w = __builtin_amdgcn_readfirstlane((int)(w_rep == 0.0 && w_p == 1.0)) != 0;
   // the replica's history record: slot values are sums over its stripes (max for GMAX);
   // this workgroup adds to stripe tile % stripes (bounded atomic contention per address)
   const size_t stripe_len = (size_t)a.slots * SPGG_NSTAT;
@@ -1376,6 +1403,14 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // plus counts for the payoffs of phases 1b / 1c (their barrier: after phase 1a) and, for the
   // recomputed NI record, of iteration t-1 (BOTH: one pass builds the two planes)
   const bool rec_prev = RECOMP && pending && kappa != 0.0;  // workgroup-uniform
+  // S_t bytes of the owned agents (PREV: read here, for the pass below and phase 1a, and held as
+  // the zero-extended words the loads return)
+  std::conditional_t<PREV, uint32_t, uint8_t> sb[APT];
+  double rprev[PREV ? APT : 1];  // PREV: their rewards of iteration t-1 (rec_prev)
+  if constexpr (PREV) {
+#pragma unroll
+    for (int u = 0; u < APT; ++u) sb[u] = sSv[cs_of(rc[u])];
+  }
   if constexpr (BOTH) {
     if (!fin_only || rec_prev)
       build_plus_counts_both_dw<(TWC + 2 * HA + 2 + 3) / 4, PCP>(sPC, sPP, sS, ly.sw, ah + 2, soffS, rec_prev, tid);
@@ -1388,20 +1423,50 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   if (rec_prev) {
     if constexpr (!BOTH) build_plus_counts_prev(sPP, sSv, ly.sw, ah + 2, tid);
     __syncthreads();  // both plus-count planes
-    const int dr = kBlock / aw, dc = kBlock - (kBlock / aw) * aw;
-    int ry = tid / aw, rx = tid - (tid / aw) * aw;
-    for (int k = tid; k < aw * ah; k += kBlock) {
-      const uint8_t b = sSv[(ry + (HS - HA)) * ly.sw + (rx + (HS - HA))];
-      const double P = payoff_pc<PCP>(sPP, ry, rx, tab + (((b >> 3) & 1) ? 6 : 0), hp.norm_min, hp.norm_den,
-                                      hp.norm_rcp);
-      const double rr = (b & 1) ? 0.0 : 0.5;                    // a_{t-1} = S_t (spgg.py:424-427)
-      const double wpp = w_p * P, wrr = w_rep * rr;
-      sRew[ry * ly.aw + rx] = wpp + wrr;
-      ry += dr;
-      rx += dc;
-      if (rx >= aw) {
-        rx -= aw;
-        ++ry;
+    if constexpr (PREV) {
+      // per slot: the thread's own agents (the slot word holds their region cell, which is their
+      // plus-count cell too), kept for phase 1a; a shadow slot writes its agent's identical value
+      // (the payoffs first, then the weights of all slots behind one branch)
+#pragma unroll
+      for (int u = 0; u < APT; ++u)
+        rprev[u] = payoff_pc<PCP>(sPP, 0, ca_of(rc[u]), tab + (((sb[u] >> 3) & 1) ? 6 : 0), hp.norm_min,
+                                  hp.norm_den, hp.norm_rcp);
+      if (!unit_w) {
+#pragma unroll
+        for (int u = 0; u < APT; ++u)                              // a_{t-1} = S_t (spgg.py:424-427)
+          rprev[u] = reward_of<SLOT>(false, rprev[u], !(sb[u] & 1), w_p, w_rep);
+      }
+#pragma unroll
+      for (int u = 0; u < APT; ++u) sRew[ca_of(rc[u])] = rprev[u];
+      // the ring cells, mapped as in phase 1c: tile + ring holds every cell phase 1a reads (an
+      // owned agent's four axial neighbours; the region's four corners are not among them)
+#pragma unroll
+      for (int j = 0; j < RP; ++j) {
+        const int k = tid + j * kBlock;
+        if (k >= ring) break;
+        int ay, ax;
+        spgg_impl::ring_cell(k, th, tw, HA, &ay, &ax);
+        const uint8_t b = sSv[(ay + (HS - HA)) * ly.sw + (ax + (HS - HA))];
+        const double P = payoff_pc<PCP>(sPP, ay, ax, tab + (((b >> 3) & 1) ? 6 : 0), hp.norm_min, hp.norm_den,
+                                        hp.norm_rcp);
+        sRew[ay * ly.aw + ax] = reward_of<SLOT>(unit_w, P, !(b & 1), w_p, w_rep);
+      }
+    } else {
+      const int dr = kBlock / aw, dc = kBlock - (kBlock / aw) * aw;
+      int ry = tid / aw, rx = tid - (tid / aw) * aw;
+      for (int k = tid; k < aw * ah; k += kBlock) {
+        const uint8_t b = sSv[(ry + (HS - HA)) * ly.sw + (rx + (HS - HA))];
+        const double P = payoff_pc<PCP>(sPP, ry, rx, tab + (((b >> 3) & 1) ? 6 : 0), hp.norm_min, hp.norm_den,
+                                        hp.norm_rcp);
+        const double rr = (b & 1) ? 0.0 : 0.5;                    // a_{t-1} = S_t (spgg.py:424-427)
+        const double wpp = w_p * P, wrr = w_rep * rr;
+        sRew[ry * ly.aw + rx] = wpp + wrr;
+        ry += dr;
+        rx += dc;
+        if (rx >= aw) {
+          rx -= aw;
+          ++ry;
+        }
       }
     }
     __syncthreads();  // rewards of iteration t-1
@@ -1444,11 +1509,11 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     float pct = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = 0.0;
-    uint8_t sb[APT];  // S_t bytes of the owned agents: s_t (bit 0) and the state (bit 4) go to rc
+    // S_t bytes of the owned agents: s_t (bit 0) and the state (bit 4) go to rc
 #pragma unroll
     for (int u = 0; u < APT; ++u) {
       if constexpr (SLOT) {
-        sb[u] = sSv[cs_of(rc[u])];
+        if constexpr (!PREV) sb[u] = sSv[cs_of(rc[u])];  // (PREV: read with the previous rewards)
       } else {
         const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
         sb[u] = sSv[(r + HS) * ly.sw + (c + HS)];
@@ -1459,7 +1524,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
 #pragma unroll
       for (int u = 0; u < APT; ++u) {
         const double vmu = owned(u) ? 1.0 : 0.0;
-        const uint8_t b = sb[u];
+        const auto b = sb[u];
         const int e = pending_entry(b);
         // kappa == 0 (a replica-uniform skip): nu = +0, q + 0 == q (Q never holds -0.0:
         // U(-0.01,0.01) draws and TD sums of finite values give +0 for exact zeros),
@@ -1475,8 +1540,9 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
               const int r = rc[u] >> 16, c = (rc[u] >> 8) & 0xff;
               ca = (r + HA) * ly.aw + (c + HA);
             }
-            mdp = prev_max_diff<M2>(sRew, ca, ly.aw);
-            atdv = prev_diag_td<ALG>(q[u], qb[u], e, (b >> 4) & 1, sRew[ca], hp, eps_prev, &qe);
+            const double r0 = PREV ? rprev[PREV ? u : 0] : sRew[ca];  // the agent's own reward of t-1
+            mdp = prev_max_diff<M2>(sRew, r0, ca, ly.aw);
+            atdv = prev_diag_td<ALG>(q[u], qb[u], e, (b >> 4) & 1, r0, hp, eps_prev, &qe);
           } else {
             mdp = md_own[u];
             atdv = atd_own[u];
@@ -1603,9 +1669,16 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       select_row<QB>(q[u], qb[u], so, &qs0, &qs1);
       const int act = ex ? rbt : greedy2(qs0, qs1);         // argmax ties -> 0
       const RVal<RQ> rn = rep_next<RQ>(r_t, act, hp);
-      const double rr = act == 0 ? 0.5 : 0.0;               // spgg.py:424-427
-      const double wpp = w_p * P, wrr = w_rep * rr;
-      const double rew = wpp + wrr;
+      double rew, wrr = 0.0;                                // spgg.py:424-427
+      if (unit_w) {
+        rew = P;
+      } else {
+        if constexpr (SLOT) asm volatile("");               // (a branch, not selects: reward_of)
+        const double rr = act == 0 ? 0.5 : 0.0;
+        const double wpp = w_p * P;
+        wrr = w_rep * rr;
+        rew = wpp + wrr;
+      }
       sA[ca] = (uint8_t)act;
       sRn[ca] = (RT)rn;
       sRew[ca] = rew;  // (R_{t+1} is stored in phase 2: a store here would make the ring's
@@ -1663,12 +1736,10 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       else draw_pair<RNG>(a, rep, g, t, pkey, eps53, 0, &ex, &rbt);
       const int act = ex ? rbt : (QB ? greedy2(mean2(v0, w0), mean2(v1, w1)) : greedy2(v0, v1));
       const RVal<RQ> rn = rep_next<RQ>(r_t, act, hp);
-      const double rr = act == 0 ? 0.5 : 0.0;
       const int ca = ay * ly.aw + ax;
       sA[ca] = (uint8_t)act;
       sRn[ca] = (RT)rn;
-      const double wpp = w_p * P, wrr = w_rep * rr;
-      sRew[ca] = wpp + wrr;
+      sRew[ca] = reward_of<SLOT>(unit_w, P, act == 0, w_p, w_rep);
     }
   }
   __syncthreads();

@@ -2,7 +2,7 @@
 barrier segment and per source function.
 
     python tools/issue_ledger.py [--tu 0] [--instance false,false,true,2,4,40,0] [--top 25]
-                                 [--asm file.s] [--keep file.s]
+                                 [--asm file.s] [--keep file.s] [--trips SEG=N[,SEG=N...]]
 
 Rebuilds one translation unit of csrc/spgg_kernels.hip to gfx950 assembly with the build's own
 compiler and flags (spgg_amd.build: HIPCC, FLAGS, the defines of that unit in UNITS) plus -gline-tables-only (line
@@ -13,6 +13,11 @@ Weights (MI355X: a wave64 op issues over a 32-lane SIMD datapath): 2 cycles for 
 op, 4 for f64 / 64-bit ops, 8 for the quarter-rate 32-bit multiplies and v_mad_u64_u32 and for
 v_rcp_f64.  Counts are static: a loop body counts once, whatever its trip count.
 Instructions are counted by class (the v_ / s_ / ds_ / global_ prefixes) alone.
+
+--trips SEG=N weights the loop bodies of barrier segment SEG by the stated trip count N (a
+fraction is a mean over the waves: 1134 cells / 256 threads = 4.43): the instructions between a
+label and the last branch back to it count N times, the rest of the segment once.  The weighted
+totals are printed beside the static ones; a segment without a backward branch is unchanged.
 
 A line belongs to the function whose definition encloses it in its source file (the innermost
 inlined callee the line tables name), and to the segment between the s_barriers around it.
@@ -85,6 +90,53 @@ def function_map(path):
     return owner
 
 
+def parse_trips(text):
+    """'2=4.43,5=3' -> {2: 4.43, 5: 3.0}"""
+    out = {}
+    for item in filter(None, (text or "").split(",")):
+        k, _, v = item.partition("=")
+        out[int(k)] = float(v)
+    return out
+
+
+_LABEL = re.compile(r"^([\w$.]+):")
+_BRANCH = re.compile(r"^\s*s_c?branch\w*\s+([\w$.]+)")
+
+
+def loop_lines(lines):
+    """Indices of `lines` inside a loop body: from a label to the last branch that names it from
+    below (a backward branch), both ends included."""
+    label_at, inside = {}, set()
+    for i, l in enumerate(lines):
+        m = _LABEL.match(l)
+        if m:
+            label_at[m.group(1)] = i
+            continue
+        b = _BRANCH.match(l)
+        if b and b.group(1) in label_at:
+            inside.update(range(label_at[b.group(1)], i + 1))
+    return inside
+
+
+def weighted_segments(body, trips):
+    """(valu, cycles) per barrier segment of a kernel body (its lines after the symbol, up to the
+    function's end), loop bodies of segment SEG counted trips[SEG] times."""
+    loops = loop_lines(body)
+    seg = [[0.0, 0.0]]
+    for i, l in enumerate(body):
+        t = l.strip()
+        if not l.startswith("\t") or not t or t.startswith((".", ";")):
+            continue
+        op = t.split()[0]
+        if op == "s_barrier":
+            seg.append([0.0, 0.0])
+        elif op.startswith("v_"):
+            n = trips.get(len(seg) - 1, 1.0) if i in loops else 1.0
+            seg[-1][0] += n
+            seg[-1][1] += n * weight(op)
+    return seg
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tu", type=int, default=0)
@@ -92,6 +144,7 @@ def main():
     ap.add_argument("--top", type=int, default=25, help="source lines listed")
     ap.add_argument("--asm", default=None)
     ap.add_argument("--keep", default=None)
+    ap.add_argument("--trips", default="", help="SEG=N[,SEG=N...]: trip count of segment SEG's loop bodies")
     a = ap.parse_args()
     path = a.asm or assemble(a.tu, a.keep)
     s = open(path).read().split("\n")
@@ -107,6 +160,9 @@ def main():
             if m:
                 d, f = (m.group(2), m.group(3)) if m.group(3) else ("", m.group(2))
                 files[m.group(1)] = f if os.path.isabs(f) else os.path.join(d, f)
+    end = next((i for i in range(st + 1, len(s)) if s[i].startswith(".Lfunc_end")), len(s))
+    trips = parse_trips(a.trips)
+    wseg = weighted_segments(s[st + 1:end], trips) if trips else None
     fmaps = {}
     seg = [collections.Counter()]
     fn = collections.defaultdict(collections.Counter)
@@ -157,10 +213,14 @@ def main():
     print(f"static VALU {nv}  weighted VALU cycles {tot}  SALU {sum(c['salu'] for c in seg)}  "
           f"LDS {sum(c['lds'] for c in seg)}  VMEM {sum(c['vmem'] for c in seg)}  " +
           "  ".join(f"{k} {v}" for k, v in sorted(meta.items())))
+    if wseg:
+        print(f"with --trips {a.trips}: VALU {sum(w[0] for w in wseg):.0f}  weighted VALU cycles "
+              f"{sum(w[1] for w in wseg):.0f}  (loop bodies of those segments at their trip counts)")
     print("\nper barrier segment")
     for i, c in enumerate(seg):
+        more = f"  at {trips[i]:g} trips: valu {wseg[i][0]:7.1f}  cyc {wseg[i][1]:7.1f}" if wseg and i in trips else ""
         print(f"  seg {i:2d}: valu {c['valu']:5d}  cyc {c['cyc']:5d} ({100 * c['cyc'] / max(tot, 1):4.1f}%)  "
-              f"salu {c['salu']:4d}  lds {c['lds']:4d}  vmem {c['vmem']:3d}")
+              f"salu {c['salu']:4d}  lds {c['lds']:4d}  vmem {c['vmem']:3d}{more}")
     print("\nper source function (weighted cycles by segment)")
     for name, c in sorted(fn.items(), key=lambda kv: -kv[1]["cyc"]):
         segs = " ".join(f"s{i}:{c[f'seg{i}']}" for i in range(len(seg)) if c[f"seg{i}"])
