@@ -70,6 +70,7 @@ class Record:
     rep_units_max: float       # max over t of sum |R_t / unit| (the int8 path's integer sum), else 0
     final: dict                # the oracle's final state
     terms: dict                # (t, k) -> per-agent terms of the float slots (keep_terms), else {}
+    rows: tuple = None         # the iterations whose accumulated float slots were evaluated (None: all)
 
 
 def oracle_params(params, L, T, M2, state, algorithm):
@@ -100,12 +101,20 @@ def _fsum(x):
     return math.fsum(np.asarray(x, dtype=np.float64).ravel().tolist())
 
 
-def exact_record(params, L, T, M2, state, algorithm, rs=None, draws=None, init=None, keep_terms=False):
+def exact_record(params, L, T, M2, state, algorithm, rs=None, draws=None, init=None, keep_terms=False, rows=None):
     """The exact history record of one replica.
 
     rs: the RandomState of a RandomState run (init None: it also makes SPGG.__init__'s draws, as
     engine.reference_init does); draws: i -> draw dict of a counter-based run (oracle/philox.py);
-    init: an object with Q, S and (Double-Q) tables replacing the initial draws."""
+    init: an object with Q, S and (Double-Q) tables replacing the initial draws.
+
+    rows: the iterations at which the accumulated float slots -- all that goes through put(), and
+    pay_mag -- are evaluated (math.fsum is most of a record's cost: a long run pays it on the
+    rows it looks at); the other rows keep 0 there.  The counters, the group composition and GMAX
+    are filled on every row whatever `rows` is, and keep_terms keeps the terms of those rows only.
+    None: every row."""
+    rows = None if rows is None else tuple(sorted({int(t) for t in rows}))
+    on_row = (lambda t: True) if rows is None else frozenset(rows).__contains__
     p = oracle_params(params, L, T, M2, state, algorithm)
     n = L * L
     if init is None:
@@ -126,6 +135,8 @@ def exact_record(params, L, T, M2, state, algorithm, rs=None, draws=None, init=N
     norm_den = 4 * p.r - (p.r - 5)
 
     def put(t, k, x):
+        if not on_row(t):
+            return
         x = np.asarray(x, dtype=np.float64).ravel()
         val[t, k] = _fsum(x)
         mag[t, k] = _fsum(np.abs(x))
@@ -137,7 +148,8 @@ def exact_record(params, L, T, M2, state, algorithm, rs=None, draws=None, init=N
         gc = np.array([np.sum(nd == d) for d in range(6)], dtype=np.float64)
         val[t, GC0:GC0 + 6] = gc
         raw = sum(gc[d] * ((5 - d) * abs(pay_c[5 - d]) + d * abs(pay_d[5 - d])) for d in range(6))
-        pay_mag[t + 1] = (raw + n * abs(p.r - 5)) / abs(norm_den)
+        if on_row(t + 1):
+            pay_mag[t + 1] = (raw + n * abs(p.r - 5)) / abs(norm_den)
 
     def start(t, S, R, P):     # iteration-start values of t (spgg.py:380-394)
         val[t, NCOOP] = np.sum(S == 0)
@@ -176,7 +188,7 @@ def exact_record(params, L, T, M2, state, algorithm, rs=None, draws=None, init=N
             put(i, SUMQ + e, qv)
             put(i, SUMQ_C + e, qv[ps == 0])
             put(i, SUMQ_D + e, qv[ps == 1])
-        if keep_terms:
+        if keep_terms and on_row(i):
             # the lattice-shaped operands, for a model of the device's summation order
             terms[(i, "grids")] = dict(prev_S=ps.copy(), actions=a.copy(), Q=Q.copy(), rew=rew.copy(), wr=wr.copy(),
                                        nu=nu.copy(), atd2=d["_atd2"].copy(), R=R_start.copy())
@@ -190,15 +202,17 @@ def exact_record(params, L, T, M2, state, algorithm, rs=None, draws=None, init=N
             group_comp(0, fin["S"])
         start(stop, fin["S"], fin["R"], fin["P"])
     return Record(value=val, mag=mag, pay_mag=pay_mag, last=last, stop_iter=stop, n=n, params=p,
-                  rep_dyadic=unit is not None, rep_units_max=state_["units"], final=fin, terms=terms)
+                  rep_dyadic=unit is not None, rep_units_max=state_["units"], final=fin, terms=terms,
+                  rows=rows)
 
 
-def philox_record(L, T, params, seed, stream_id, M2, state, algorithm="qlearning", init=None, keep_terms=False):
+def philox_record(L, T, params, seed, stream_id, M2, state, algorithm="qlearning", init=None, keep_terms=False,
+                  rows=None):
     """exact_record under the Philox draws of (seed, stream_id), initialised as the engine
     initialises a replica: SPGG.__init__'s draws from RandomState(seed) unless init is given."""
     key = PH.philox_key(int(seed or 0), stream_id)
     rs = None if init is not None else np.random.RandomState(seed)
-    return exact_record(params, L, T, M2, state, algorithm, rs=rs, init=init, keep_terms=keep_terms,
+    return exact_record(params, L, T, M2, state, algorithm, rs=rs, init=init, keep_terms=keep_terms, rows=rows,
                         draws=lambda i: PH.draws(key, L, i, algorithm))
 
 
@@ -364,3 +378,18 @@ def mismatches(got, rec, bound, rows=None, skip=()):
             if not abs(g - w) <= bd:        # (a NaN fails)
                 bad.append((t, SLOT_NAMES[k], g, w, bd))
     return bad
+
+
+def mismatches_on_rows(got, rec, bound):
+    """mismatches() for a record made with `rows`: the counters and GMAX, which exact_record fills
+    on every row, on every row (their bound is 0: bit-equal); the other slots where the record
+    holds them -- on rec.rows, and past rec.last, where nothing is accumulated and every slot of
+    the record is 0 whatever `rows` was.  rec.rows None: mismatches(got, rec, bound)."""
+    if rec.rows is None:
+        return mismatches(got, rec, bound)
+    every = COUNTERS + (GMAX,)
+    assert not bound[:, list(every)].any()
+    T2 = rec.value.shape[0]
+    held = sorted({t for t in rec.rows if 0 <= t < T2} | set(range(rec.last + 1, T2)))
+    bad = mismatches(got, rec, bound, skip=[k for k in range(NSTAT) if k not in every])
+    return sorted(bad + mismatches(got, rec, bound, rows=held, skip=every), key=lambda m: m[0])

@@ -151,13 +151,10 @@ def model_ratio(rec, t, tile, rng, ulps):
     return fold(tile_totals(term, tile) * 100.0, tile[3], rng)
 
 
-@pytest.mark.parametrize("L,alg,M2,gain", ALL_CASES)
-def test_reference_in_device_order_stays_inside_f64_bounds(L, alg, M2, gain):
-    rec = _rec(L, alg, M2, gain)
-    assert rec.rep_dyadic == _dyadic(gain)
+def _check_f64(rec, L, steps):
     b = R.bounds(rec)
     rng = np.random.RandomState(L)
-    for t in _steps(rec):
+    for t in steps:
         got = model_f64_slots(rec, t, TILES[L], rng)
         for ulps in (-1, 0, 1):
             got[(R.SUM_RATIO_C, ulps)] = model_ratio(rec, t, TILES[L], rng, ulps)
@@ -165,6 +162,13 @@ def test_reference_in_device_order_stays_inside_f64_bounds(L, alg, M2, gain):
             k = k[0] if isinstance(k, tuple) else k
             err = abs(v - rec.value[t, k])
             assert err <= b[t, k], (t, R.SLOT_NAMES[k], v, rec.value[t, k], b[t, k])
+
+
+@pytest.mark.parametrize("L,alg,M2,gain", ALL_CASES)
+def test_reference_in_device_order_stays_inside_f64_bounds(L, alg, M2, gain):
+    rec = _rec(L, alg, M2, gain)
+    assert rec.rep_dyadic == _dyadic(gain)
+    _check_f64(rec, L, _steps(rec))
 
 
 def test_int8_reputation_sum_is_representable():
@@ -197,10 +201,10 @@ def model_finalize(p, gc, nc, nc1, n, sw_cd, rew_c):
             R.SUM_REW_D: (wpp + wrr) - rew_c, R.SW_DC: sw_cd + nc1 - nc}
 
 
-def _check_finalize(rec, rew_c_of):
+def _check_finalize(rec, rew_c_of, steps=None):
     b = R.bounds(rec)
     v = rec.value
-    for t in _steps(rec):
+    for t in _steps(rec) if steps is None else steps:
         got = model_finalize(rec.params, v[t - 1, R.GC0:R.GC0 + 6], v[t, R.NCOOP], v[t + 1, R.NCOOP], rec.n,
                              v[t, R.SW_CD], rew_c_of(t))
         for k, x in got.items():
@@ -246,9 +250,13 @@ def model_pct(rec, t, tile, rng, ulps):
 @pytest.mark.parametrize("L,alg,M2,gain", ALL_CASES)
 def test_reference_in_f32_chain_stays_inside_pct_bound(L, alg, M2, gain):
     rec = _rec(L, alg, M2, gain)
+    _check_pct(rec, L, _steps(rec))
+
+
+def _check_pct(rec, L, steps):
     b = R.bounds(rec)
     rng = np.random.RandomState(L + 2)
-    for t in _steps(rec):
+    for t in steps:
         if rec.params.influence_factor == 0.0:      # nu = +0: the slot and its bound are exactly 0
             assert rec.value[t, R.SUM_PCT] == 0.0 and b[t, R.SUM_PCT] == 0.0
         else:
@@ -289,6 +297,10 @@ def test_one_agent_moves_a_sum_by_far_more_than_its_bound(L, alg, M2, gain):
     SUM_PCT cannot be relied on to see one agent in 10^6 ("Precision of the history
     record")."""
     rec = _rec(L, alg, M2, gain)
+    _check_sensitivity(rec, L, _steps(rec))
+
+
+def _check_sensitivity(rec, L, steps):
     b = R.bounds(rec)
     slots = [k for k in R.F64_SUM_SLOTS + R.REGROUPED if not (k == R.SUMR and rec.rep_dyadic)]
     # slots whose every term the parameters make exactly 0 (their bounds are 0 too: bit-equal on the
@@ -299,7 +311,7 @@ def test_one_agent_moves_a_sum_by_far_more_than_its_bound(L, alg, M2, gain):
         slots = [k for k in slots if k not in (R.SUM_WPP, R.SUM_REW_D)]
         assert not b[:, R.SUM_WPP].any()
     seen = set()
-    for t in _steps(rec):
+    for t in steps:
         for k in slots:
             med = _median_term(rec, t, k)
             if med is None:         # (no reputation yet at t = 1: R_1 = 0)
@@ -326,3 +338,46 @@ def test_one_agent_moves_a_sum_by_far_more_than_its_bound(L, alg, M2, gain):
         else:
             assert med < 2 * b[t, R.SUM_PCT] and med < 100 * b[t, R.SUM_PCT], (t, med, b[t, R.SUM_PCT])
     assert seen == set(slots)
+
+
+# ---- 4. the same at late rows ----------------------------------------------------------------------
+# Past the eps floor most reputations sit at a bound, few strategies flip, and the prev-D agents whose
+# Q sums the kernel forms as total - prev-C are most of the lattice or very few of it (tests/_deep.py).
+# The derivations of R.bounds make no assumption about any of that -- the any-order bound is relative
+# to sum|x| whatever the terms are, SUMQ_D adds its two parts' bounds whatever their ratio -- so they
+# stand as they are; what a late row could break is the margin between the models and the bounds,
+# and between the bounds and one agent's term, which is what is held here.  The records are sparse
+# (rows = LATE_ROWS): one oracle run of 600 iterations each.
+LATE_ROWS = (390, 600)
+# (L, operator, M2, replica of its tests/_deep batch); the share of prev-D agents at t = 600: 0.009, 0.82
+# (kappa = 0: the NI percent and its bound are exactly 0), 0.11, 0.39, 0.55
+LATE_CASES = [(30, "qlearning", True, 2), (30, "qlearning", False, 0), (30, "double_qlearning", True, 1),
+              (120, "qlearning", False, 0), (120, "double_qlearning", False, 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def _late(L, alg, M2, k):
+    from tests import _deep as D
+    b = [b for g in (D.A[3:], D.C, D.D) for b in g if (b.L, b.alg, b.M2, b.state) == (L, alg, M2, "reputation")][0]
+    return R.philox_record(L, D.T, b.rows[k], b.seeds[k], k, M2, "reputation", alg, keep_terms=True, rows=LATE_ROWS)
+
+
+@pytest.mark.parametrize("L,alg,M2,k", LATE_CASES)
+def test_late_rows_stay_inside_bounds_and_one_agent_far_outside(L, alg, M2, k):
+    rec = _late(L, alg, M2, k)
+    assert rec.stop_iter == 0 and rec.rows == LATE_ROWS and rec.rep_dyadic
+    assert {t for t, key in rec.terms if key == "grids"} == set(LATE_ROWS)
+    p = rec.params
+    assert p.reward_weight_rep != 0.0
+    for t in LATE_ROWS:
+        g = rec.terms[(t, "grids")]
+        at_bound = np.mean((g["R"] == p.R_min) | (g["R"] == p.R_max))
+        prev_d = np.mean(g["prev_S"] == 1)
+        print("L", L, alg, "t", t, "R at a bound %.3f" % at_bound, "prev-D %.3f" % prev_d,
+              "flips", int(rec.value[t, R.SW_CD] + rec.value[t, R.SW_DC]))
+        assert at_bound > 0.5, (t, at_bound)       # the late lattice, not the early one
+    _check_f64(rec, L, LATE_ROWS)
+    rng = np.random.RandomState(L + 1)
+    _check_finalize(rec, lambda t: model_f64_slots(rec, t, TILES[L], rng)[R.SUM_REW_C], LATE_ROWS)
+    _check_pct(rec, L, LATE_ROWS)
+    _check_sensitivity(rec, L, LATE_ROWS)
