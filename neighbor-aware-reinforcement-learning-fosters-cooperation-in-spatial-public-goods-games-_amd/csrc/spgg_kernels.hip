@@ -106,6 +106,7 @@ struct TileArgs {
 struct LaunchCfg {
   int m2, as, rq, rng, twc, total_tiles;
   int apt;  // agents per thread: apt_of(alg), or 1 for small batches
+  int thc;  // compile-time tile height (kTileH: every tile of the lattice is that high), or 0
   size_t lds_bytes;
 };
 
@@ -156,6 +157,14 @@ constexpr int ring_per_thread(bool m2) { return kBlock == 256 && m2 ? 2 : 1; }
 // Doubles per agent in Q and fields per border record (Double-Q: both tables).
 constexpr int qw_of(int alg) { return alg == SPGG_ALG_DOUBLE_Q ? 8 : 4; }
 constexpr int pf_of(int alg) { return alg == SPGG_ALG_DOUBLE_Q ? 5 : 3; }
+// The slot-word instances (step_impl's SLOT: first order, Philox, the operator's most agents per
+// thread at the compile-time width 40, one table).  Each has the twin plus-count planes (payoff_twin)
+// and two forms: tile height kTileH at compile time (spgg_step_kernel), where every tile of the
+// lattice is that high, and the run-time height (spgg_step_kernel_rth).
+constexpr bool slot_instance(bool m2, int rng, int apt, int twc, int alg) {
+  return !m2 && rng == SPGG_RNG_PHILOX && twc == 40 && apt == apt_of(alg) && alg != SPGG_ALG_DOUBLE_Q;
+}
+constexpr int kTileH = 25;  // the chooser's tile height where 25 divides L (L = 200, 1000)
 
 // Border records.  An agent within HA cells of its tile's edge is read by the
 // ring recompute of a neighbouring tile (every ring cell of a tile is a border
@@ -234,9 +243,10 @@ constexpr int kPcPitch = 64;
 // dword_rows (compile-time-width kernels): every plane has one dword-aligned
 // pitch wide enough for a window staged as aligned dwords (window column j at
 // plane column j + its 0..3-byte misalignment).
-__host__ __device__ inline LdsLayout lds_layout(int tw, int th, int HS, int HA, int rsz, bool dword_rows = false,
-                                                bool draws = false) {
-  LdsLayout l;
+// twin (the slot-word instances): a second plus-count plane behind the first (payoff_twin).
+__host__ __device__ constexpr LdsLayout lds_layout(int tw, int th, int HS, int HA, int rsz, bool dword_rows = false,
+                                                   bool draws = false, bool twin = false) {
+  LdsLayout l{};
   l.sw = tw + 2 * HS; l.sh = th + 2 * HS;
   l.aw = tw + 2 * HA; l.ah = th + 2 * HA;
   if (dword_rows) l.sw = l.aw = (tw + 2 * HS + 3 + 3) / 4 * 4;
@@ -249,7 +259,7 @@ __host__ __device__ inline LdsLayout lds_layout(int tw, int th, int HS, int HA, 
   l.off_S = off;    off += ((l.sw * l.sh + 15) / 16) * 16;
   l.off_D = off;    off += ((l.sw * l.sh + kPcPitch + 15) / 16) * 16;  // + slack: full-wave row reads
   l.off_A = off;    off += ((na + 15) / 16) * 16;
-  l.off_PC = off;   off += (l.ah + 2) * l.pcp;
+  l.off_PC = off;   off += (l.ah + 2) * l.pcp * (twin ? 2 : 1);
   off = (off + 15) / 16 * 16;
   l.off_DR = off;   off += draws ? l.ah * kDrawSlots * 2 * 4 : 0;
   l.off_DP = off;   off += draws ? l.ah * 2 * 2 * 4 : 0;
@@ -500,6 +510,10 @@ __device__ __forceinline__ void build_plus_counts(uint8_t* pc, const uint8_t* d,
   }
 }
 
+// The twin of a plus-count plane holds every byte + 48 = the offset of pay_d, which follows pay_c by
+// six doubles, so a twin byte indexes the defector's table from the cooperator's base.
+constexpr uint32_t kTwinBytes = 0x30303030u;
+
 // The same plane for compile-time-width tiles, four cells per lane: the defector plane
 // (window column j at physical column j + soff, soff <= 1, rows dword-aligned) is read
 // as aligned dwords and the five neighbour bytes of four consecutive cells are funnel
@@ -507,9 +521,10 @@ __device__ __forceinline__ void build_plus_counts(uint8_t* pc, const uint8_t* d,
 // carries into the next; bytes past the window (uninitialised) feed only higher, unused
 // bytes.  DWPR = dwords per plane row (>= the region width + 2, / 4); PCP = the plane's pitch in
 // bytes (a multiple of 4, >= 4 DWPR).
-template <int DWPR, int PCP>
+// TWIN: the plane's twin, every byte + 48, at pc + twin (payoff_twin).
+template <int DWPR, int PCP, bool TWIN = false>
 __device__ __forceinline__ void build_plus_counts_dw(uint8_t* pc, const uint8_t* dplane, int sw, int rows,
-                                                     int soff, int tid) {
+                                                     int soff, int tid, int twin = 0) {
   const uint32_t s0 = 8u * soff, s1 = s0 + 8u, s2 = s0 + 16u;
   const int swd = sw >> 2;
   for (int task = tid; task < rows * DWPR; task += kBlock) {
@@ -522,6 +537,7 @@ __device__ __forceinline__ void build_plus_counts_dw(uint8_t* pc, const uint8_t*
                          __builtin_amdgcn_alignbit(b1, b0, s1) + __builtin_amdgcn_alignbit(b1, b0, s2) +
                          __builtin_amdgcn_alignbit(c1, c0, s1);
     *reinterpret_cast<uint32_t*>(pc + y * PCP + xd * 4) = cnt << 3;
+    if constexpr (TWIN) *reinterpret_cast<uint32_t*>(pc + twin + y * PCP + xd * 4) = (cnt << 3) + kTwinBytes;
   }
 }
 
@@ -543,9 +559,10 @@ __device__ __forceinline__ void build_plus_counts_prev(uint8_t* pc, const uint8_
 // defector count of S_t in bits 0-2 and that of S_{t-1}, already x8, in bits 3-5 (<= 5 + 40: no
 // byte carries into the next).  pc gets the first x8, pp (when `prev`: workgroup-uniform) the
 // second; one set of LDS reads and funnel shifts instead of two, and no defector-bit plane.
-template <int DWPR, int PCP>
+// TWIN: each plane's twin, every byte + 48 (<= 40 + 48: no carry), at the plane + twin (payoff_twin).
+template <int DWPR, int PCP, bool TWIN = false>
 __device__ __forceinline__ void build_plus_counts_both_dw(uint8_t* pc, uint8_t* pp, const uint8_t* splane, int sw,
-                                                          int rows, int soff, bool prev, int tid) {
+                                                          int rows, int soff, bool prev, int tid, int twin = 0) {
   const uint32_t s0 = 8u * soff, s1 = s0 + 8u, s2 = s0 + 16u;
   const int swd = sw >> 2;
   constexpr uint32_t kB03 = 0x09090909u;
@@ -558,8 +575,13 @@ __device__ __forceinline__ void build_plus_counts_both_dw(uint8_t* pc, uint8_t* 
     const uint32_t cnt = __builtin_amdgcn_alignbit(a1, a0, s1) + __builtin_amdgcn_alignbit(b1, b0, s0) +
                          __builtin_amdgcn_alignbit(b1, b0, s1) + __builtin_amdgcn_alignbit(b1, b0, s2) +
                          __builtin_amdgcn_alignbit(c1, c0, s1);
-    *reinterpret_cast<uint32_t*>(pc + y * PCP + xd * 4) = (cnt & 0x07070707u) << 3;
-    if (prev) *reinterpret_cast<uint32_t*>(pp + y * PCP + xd * 4) = cnt & 0x38383838u;
+    const uint32_t c8 = (cnt & 0x07070707u) << 3, p8 = cnt & 0x38383838u;
+    *reinterpret_cast<uint32_t*>(pc + y * PCP + xd * 4) = c8;
+    if constexpr (TWIN) *reinterpret_cast<uint32_t*>(pc + twin + y * PCP + xd * 4) = c8 + kTwinBytes;
+    if (prev) {
+      *reinterpret_cast<uint32_t*>(pp + y * PCP + xd * 4) = p8;
+      if constexpr (TWIN) *reinterpret_cast<uint32_t*>(pp + twin + y * PCP + xd * 4) = p8 + kTwinBytes;
+    }
   }
 }
 
@@ -582,6 +604,25 @@ __device__ __forceinline__ double payoff_pc(const uint8_t* pc, int ry, int rx, c
   tot = tot + T_AT(t, x3);                     // group (1,1)  -> N0[i,j-1]
   tot = tot + T_AT(t, x4);                     // group (-1,1) -> N0[i,j+1]
   return div_uniform(tot - norm_min, norm_den, norm_rcp);  // (tot - (r-5)) / (4r - (r-5))
+}
+
+// The same payoff from a plane and its twin (build_plus_counts_*_dw, TWIN): the cell's own strategy
+// d (0 C, 1 D) picks the plane -- its twin lies `twin` bytes behind it -- whose bytes index the one
+// table base tb = pay_c (a twin byte carries pay_d's offset), so the only per-lane address
+// arithmetic is idx + d * twin: the table reads take the byte as their address and the base as
+// their immediate offset.  idx: the cell's index ry * PCP + rx.  Same operands, same order.
+template <int PCP>
+__device__ __forceinline__ double payoff_twin(const uint8_t* pc, int idx, uint32_t d, int twin, const double* tb,
+                                              double norm_min, double norm_den, double norm_rcp) {
+  const uint8_t* p = pc + (__umul24(d, (uint32_t)twin) + (uint32_t)idx) + 1;
+  const char* t = reinterpret_cast<const char*>(tb);
+  const uint32_t x0 = p[PCP], x1 = p[0], x2 = p[2 * PCP], x3 = p[PCP - 1], x4 = p[PCP + 1];
+  double tot = T_AT(t, x0);
+  tot = tot + T_AT(t, x1);
+  tot = tot + T_AT(t, x2);
+  tot = tot + T_AT(t, x3);
+  tot = tot + T_AT(t, x4);
+  return div_uniform(tot - norm_min, norm_den, norm_rcp);
 }
 
 #undef T_AT
@@ -1036,7 +1077,11 @@ constexpr int min_waves(bool m2, int rng, int twc, int alg) {
 // and NCOOP of the replica's history record, spgg.py:405,488, and the neighbours' S / R /
 // border records); those hand-offs are sc1 (hload / hstore).  Every workgroup of a replica takes the
 // same absorbing decision at the same iteration (NCOOP), so none waits for a stopped tile.
-template <bool M2, bool AS, bool RQ, int RNG, int APT, int TWC, int ALG, bool PERSIST>
+// THC (slot-word instances): the tile height at compile time -- every tile of the lattice is THC
+// rows high (the host: L % THC == 0) -- so th, the region, the ring, the whole LDS layout and the
+// loop bounds made from them are constants and every plane origin is part of an access's immediate
+// offset; 0: the run-time height a0.TH, the last row of tiles shorter.
+template <bool M2, bool AS, bool RQ, int RNG, int APT, int TWC, int ALG, bool PERSIST, int THC = 0>
 __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, const int fin_only,
                                           const spgg_impl::PersistArgs& pa) {
   static_assert(!PERSIST || TWC > 0, "persistent launches use the compile-time-width kernels");
@@ -1075,6 +1120,11 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   // the rewards of iteration t-1 per agent slot and ring cell instead of a loop over the region
   // (below, after the plus-count planes): the slot-word kernels that recompute the NI record
   constexpr bool PREV = SLOT && RECOMP;
+  // payoffs from the twin plus-count planes (payoff_twin)
+  constexpr bool TWIN = SLOT;
+  static_assert(SLOT == spgg_impl::slot_instance(M2, RNG, APT, TWC, ALG) || PERSIST, "the host's rule is the kernel's");
+  static_assert(THC == 0 || SLOT, "only the slot-word instances have a compile-time height");
+  const int TH = THC ? THC : a0.TH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   // XCD-aware placement: blocks b, b+8, b+16... share an XCD (round-robin
@@ -1097,14 +1147,24 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   const int L = a0.L, n = a0.n;
   const bool tiny = TWC ? false : L < 8;  // TWC => L % TWC == 0
   const int tyi = tile / a0.tiles_x, txi = tile - (tile / a0.tiles_x) * a0.tiles_x;
-  const int y0 = tyi * a0.TH, x0 = txi * a0.TW;
-  const int th = min(a0.TH, L - y0), tw = TWC ? TWC : min(a0.TW, L - x0);
+  const int y0 = tyi * TH, x0 = txi * a0.TW;
+  const int th = THC ? THC : min(a0.TH, L - y0), tw = TWC ? TWC : min(a0.TW, L - x0);
   // LDS pitches from the full tile width (constants when TWC > 0); edge tiles
   // use the top-left part of each region
-  const LdsLayout ly = TWC ? lds_layout(TWC, a0.TH, HS, HA, (int)sizeof(RT), true, DSTAGE)
+  const LdsLayout ly = TWC ? lds_layout(TWC, TH, HS, HA, (int)sizeof(RT), true, DSTAGE, TWIN)
                            : lds_layout(tw, th, HS, HA, (int)sizeof(RT));
-  double* tab = reinterpret_cast<double*>(smem);
-  double* red = tab + 12;
+  // TWIN: each plus-count plane's twin lies one plane behind it.  sPC's is part of the layout; sPP's
+  // shares the ring records' space with it (the host sizes the larger of the records and the two
+  // planes; at the compile-time height the records are the larger, checked here)
+  const int twin = (ly.ah + 2) * ly.pcp;
+  static_assert(THC == 0 || 2 * (THC + 2 * HA + 2) * PCP <=
+                                ((TWC + 2 * HA) * (THC + 2 * HA) - TWC * THC) * PF * (int)sizeof(double),
+                "both planes of S_{t-1}'s plus counts fit the ring records' space");
+  // TWIN: the payoff table in static LDS -- its address is a constant, which the table reads take
+  // as their immediate offset (the dynamic segment's base is known only as a register)
+  __shared__ double tab_twin[TWIN ? 12 : 1];
+  double* tab = TWIN ? tab_twin : reinterpret_cast<double*>(smem);
+  double* red = reinterpret_cast<double*>(smem) + 12;
   double* sRew = reinterpret_cast<double*>(smem + ly.off_Rew);
   RT* sR = reinterpret_cast<RT*>(smem + ly.off_R);
   RT* sRn = reinterpret_cast<RT*>(smem + ly.off_Rn);
@@ -1413,9 +1473,11 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
   }
   if constexpr (BOTH) {
     if (!fin_only || rec_prev)
-      build_plus_counts_both_dw<(TWC + 2 * HA + 2 + 3) / 4, PCP>(sPC, sPP, sS, ly.sw, ah + 2, soffS, rec_prev, tid);
+      build_plus_counts_both_dw<(TWC + 2 * HA + 2 + 3) / 4, PCP, TWIN>(sPC, sPP, sS, ly.sw, ah + 2, soffS, rec_prev,
+                                                                       tid, twin);
   } else if (!fin_only) {
-    if constexpr (TWC > 0) build_plus_counts_dw<(TWC + 2 * HA + 2 + 3) / 4, PCP>(sPC, sD, ly.sw, ah + 2, soffS, tid);
+    if constexpr (TWC > 0)
+      build_plus_counts_dw<(TWC + 2 * HA + 2 + 3) / 4, PCP, TWIN>(sPC, sD, ly.sw, ah + 2, soffS, tid, twin);
     else build_plus_counts(sPC, sDv, ly.sw, ah + 2, tid);
   }
   // the rewards of iteration t-1 over the region (tile + ring), into sRew (phase 1a reads them;
@@ -1429,8 +1491,8 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       // (the payoffs first, then the weights of all slots behind one branch)
 #pragma unroll
       for (int u = 0; u < APT; ++u)
-        rprev[u] = payoff_pc<PCP>(sPP, 0, ca_of(rc[u]), tab + (((sb[u] >> 3) & 1) ? 6 : 0), hp.norm_min,
-                                  hp.norm_den, hp.norm_rcp);
+        rprev[u] = payoff_twin<PCP>(sPP, ca_of(rc[u]), (sb[u] >> 3) & 1u, twin, tab, hp.norm_min, hp.norm_den,
+                                    hp.norm_rcp);
       if (!unit_w) {
 #pragma unroll
         for (int u = 0; u < APT; ++u)                              // a_{t-1} = S_t (spgg.py:424-427)
@@ -1447,8 +1509,8 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
         int ay, ax;
         spgg_impl::ring_cell(k, th, tw, HA, &ay, &ax);
         const uint8_t b = sSv[(ay + (HS - HA)) * ly.sw + (ax + (HS - HA))];
-        const double P = payoff_pc<PCP>(sPP, ay, ax, tab + (((b >> 3) & 1) ? 6 : 0), hp.norm_min, hp.norm_den,
-                                        hp.norm_rcp);
+        const double P = payoff_twin<PCP>(sPP, ay * PCP + ax, (b >> 3) & 1u, twin, tab, hp.norm_min, hp.norm_den,
+                                          hp.norm_rcp);
         sRew[ay * ly.aw + ax] = reward_of<SLOT>(unit_w, P, !(b & 1), w_p, w_rep);
       }
     } else {
@@ -1632,7 +1694,7 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
       const int ca = SLOT ? ca_of(rc[u]) : (r + HA) * ly.aw + (c + HA);
       const int s_t = (rc[u] >> 3) & 1;                     // (S_t bits, recorded in phase 1a)
       // (SLOT: the plus-count cell is the region cell, the pitches agree)
-      const double P = SLOT ? payoff_pc<PCP>(sPC, 0, ca, tab + (s_t ? 6 : 0), hp.norm_min, hp.norm_den, hp.norm_rcp)
+      const double P = SLOT ? payoff_twin<PCP>(sPC, ca, (uint32_t)s_t, twin, tab, hp.norm_min, hp.norm_den, hp.norm_rcp)
                             : payoff_pc<PCP>(sPC, r + HA, c + HA, tab + (s_t ? 6 : 0), hp.norm_min, hp.norm_den,
                                              hp.norm_rcp);
       const RVal<RQ> r_t = AS ? hload<PERSIST>(at(Rin, AGENT_U(u))) : sRv[ca];
@@ -1729,7 +1791,10 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
           }
         }
       }
-      const double P = payoff_pc<PCP>(sPC, ay, ax, tab + ((b & 1) ? 6 : 0), hp.norm_min, hp.norm_den, hp.norm_rcp);
+      const double P = TWIN ? payoff_twin<PCP>(sPC, ay * PCP + ax, b & 1u, twin, tab, hp.norm_min, hp.norm_den,
+                                               hp.norm_rcp)
+                            : payoff_pc<PCP>(sPC, ay, ax, tab + ((b & 1) ? 6 : 0), hp.norm_min, hp.norm_den,
+                                             hp.norm_rcp);
       const RVal<RQ> r_t = AS ? RVal<RQ>(0) : RVal<RQ>(sRv[ay * ly.aw + ax]);
       int ex, rbt;
       if constexpr (DSTAGE) staged_draw(sDP, ay, ax, &ex, &rbt);
@@ -1755,7 +1820,8 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
     // border_slot_or_none, and the load lands while the first agent is processed
     // (border_slot_table: the host's build_ring_table)
     const uint64_t bsw = *at(reinterpret_cast<const uint64_t*>(a.ring + (size_t)a.tiles_per_rep * a.ring_max),
-                             (uint32_t)(((th != a.TH ? 2 : 0) + (tw != a.TW ? 1 : 0)) * kBlock + tid));
+                             (uint32_t)(THC ? tid  // (every tile full height and width: shape 0)
+                                            : ((th != a.TH ? 2 : 0) + (tw != a.TW ? 1 : 0)) * kBlock + tid));
     // the stored diagnostic |alpha*td'| (kappa == 0: the NI percent it feeds is exactly 0), as a
     // scalar flag (an f64 compare has no scalar form and was repeated on the VALU per agent)
     const bool ni_on = __builtin_amdgcn_readfirstlane((int)(kappa != 0.0)) != 0;
@@ -1955,7 +2021,17 @@ __device__ __forceinline__ void step_impl(const TileArgs& a0, const int t0, cons
 template <bool M2, bool AS, bool RQ, int RNG, int APT, int TWC, int ALG>
 __global__ __launch_bounds__(kBlock, min_waves(M2, RNG, TWC, ALG)) void spgg_step_kernel(TileArgs a, int t,
                                                                                          int fin_only) {
-  step_impl<M2, AS, RQ, RNG, APT, TWC, ALG, false>(a, t, fin_only, spgg_impl::PersistArgs{});
+  constexpr int THC = spgg_impl::slot_instance(M2, RNG, APT, TWC, ALG) ? spgg_impl::kTileH : 0;
+  step_impl<M2, AS, RQ, RNG, APT, TWC, ALG, false, THC>(a, t, fin_only, spgg_impl::PersistArgs{});
+}
+
+// A slot-word instance at the run-time tile height (spgg_step_kernel of the same parameters has
+// the height kTileH at compile time): lattices whose tiles are not all kTileH rows high.
+template <bool M2, bool AS, bool RQ, int RNG, int APT, int TWC, int ALG>
+__global__ __launch_bounds__(kBlock, min_waves(M2, RNG, TWC, ALG)) void spgg_step_kernel_rth(TileArgs a, int t,
+                                                                                             int fin_only) {
+  static_assert(spgg_impl::slot_instance(M2, RNG, APT, TWC, ALG), "only the slot-word instances have two forms");
+  step_impl<M2, AS, RQ, RNG, APT, TWC, ALG, false, 0>(a, t, fin_only, spgg_impl::PersistArgs{});
 }
 
 // The persistent form: four workgroups per CU at most 128 VGPRs (cfg5's 1000 tiles of 1024
@@ -2097,6 +2173,13 @@ void launch_t(const LaunchCfg& lc, const TileArgs& a, int t, int fin, hipStream_
       else
         hipLaunchKernelGGL((spgg_step_kernel<M2, AS, RQ, RNG, 2, 0, ALG>), grid, dim3(kBlock), lc.lds_bytes, s, a,
                            t, fin);
+      return;
+    }
+  }
+  if constexpr (slot_instance(M2, RNG, APT, 40, ALG)) {
+    if (lc.twc == 40 && lc.thc != kTileH) {  // (spgg_step_kernel of these parameters: height kTileH)
+      hipLaunchKernelGGL((spgg_step_kernel_rth<M2, AS, RQ, RNG, APT, 40, ALG>), grid, dim3(kBlock), lc.lds_bytes, s,
+                         a, t, fin);
       return;
     }
   }
@@ -2600,6 +2683,7 @@ spgg_impl::LaunchCfg launch_cfg(const spgg_ctx* c) {
   lc.rng = c->cfg.rng_mode;
   lc.twc = twc_of(c->cfg, c->TW, c->TH);
   lc.apt = c->apt;
+  lc.thc = c->TH == spgg_impl::kTileH && c->cfg.L % spgg_impl::kTileH == 0 ? spgg_impl::kTileH : 0;
   lc.total_tiles = c->cfg.n_rep * c->tiles_per_rep;
   lc.lds_bytes = c->lds_bytes;
   return lc;
@@ -2920,8 +3004,11 @@ int spgg_create(spgg_ctx** out, const spgg_config* cfg) {
   while (c->stripes < 32 && (c->tiles_per_rep + c->stripes - 1) / c->stripes > tiles_per_stripe) c->stripes *= 2;
   const int HA = cfg->second_order ? 2 : 1;
   const bool twc = twc_of(*cfg, c->TW, c->TH) > 0;
+  // (the kernel's TWIN: the slot-word instances keep each plus-count plane twice)
+  const bool twin = spgg_impl::slot_instance(cfg->second_order != 0, cfg->rng_mode, c->apt,
+                                             twc_of(*cfg, c->TW, c->TH), cfg->algorithm);
   const LdsLayout ly = lds_layout(c->TW, c->TH, HA + 2, HA, cfg->rep_int8 ? 1 : 8, twc,
-                                  twc && cfg->rng_mode != SPGG_RNG_PHILOX);  // (the kernel's DSTAGE)
+                                  twc && cfg->rng_mode != SPGG_RNG_PHILOX, twin);  // (the kernel's DSTAGE)
   c->lds_bytes = (size_t)ly.bytes;
   c->PB = spgg_impl::pub_slots(c->TW, c->TH, HA);
   // stage_region's per-thread register window must cover the S and R halos
@@ -2934,7 +3021,7 @@ int spgg_create(spgg_ctx** out, const spgg_config* cfg) {
   if (!rc) rc = build_ring_table(c);
   if (!rc) {  // + the ring cells' border records (or the S_{t-1} plus-count plane that shares them)
     c->lds_bytes += std::max((size_t)c->ring_max * spgg_impl::pf_of(cfg->algorithm) * sizeof(double),
-                             (size_t)(ly.ah + 2) * ly.pcp);
+                             (size_t)(ly.ah + 2) * ly.pcp * (twin ? 2 : 1));
     if (c->lds_bytes > 160 * 1024) rc = fail(c, SPGG_E_ARG, "tile LDS footprint exceeds 160 KB");
   }
   // persistent launches (opt-in, SPGG_PERSIST=1): when the whole batch's tiles (every replica

@@ -6,7 +6,8 @@ units of csrc/spgg_kernels.hip, one source tree against another (profiles/*/inst
 Each tree's units are compiled to gfx950 assembly with that tree's own build table
 (the package's build.py: HIPCC, FLAGS, UNITS), and NumVgprs / ScratchSize / Occupancy are read
 from each kernel's trailer.  '*' marks the instances with the slot word by region index (SLOT:
-first order, Philox, compile-time width 40, four agents per thread, not Double-Q).  The lines that
+first order, Philox, compile-time width 40, four agents per thread, not Double-Q; step_rth is such
+an instance at the run-time tile height, step the one at the compile-time height).  The lines that
 differ are listed again at the end.
 """
 import argparse
@@ -39,7 +40,7 @@ def assemble(B, tu, out):
     return out
 
 
-_SYM = re.compile(r"^(_Z\w*?\d+spgg_(step|persist)_kernelI((?:L[bi]\d+E)+)E\w*):")
+_SYM = re.compile(r"^(_Z\w*?\d+spgg_(step|persist)_kernel(_rth)?I((?:L[bi]\d+E)+)E\w*):")
 _ARG = re.compile(r"L([bi])(\d+)E")
 
 
@@ -49,7 +50,7 @@ def kernels(path):
     for l in open(path):
         m = _SYM.match(l)
         if m:
-            cur, meta = f"{m.group(2)}<{','.join(a[1] for a in _ARG.findall(m.group(3)))}>", {}
+            cur, meta = f"{m.group(2)}{m.group(3) or ''}<{','.join(a[1] for a in _ARG.findall(m.group(4)))}>", {}
             continue
         if cur:
             m = re.match(r"\s*;\s*(NumVgprs|ScratchSize|Occupancy)\s*:\s*(\d+)", l)
@@ -64,7 +65,7 @@ def kernels(path):
 def is_slot(name):
     kind, args = name.split("<")
     a = [int(x) for x in args.rstrip(">").split(",")]
-    return kind == "step" and a[0] == 0 and a[3] == 2 and a[4] == 4 and a[5] == 40 and a[6] != 3
+    return kind in ("step", "step_rth") and a[0] == 0 and a[3] == 2 and a[4] == 4 and a[5] == 40 and a[6] != 3
 
 
 def main():
